@@ -12,6 +12,10 @@ Multi-GPU (torchrun, one rank per GPU, RCCL): weak scaling -- every rank rolls o
 rows (disjoint Philox sub-streams) into a staging buffer; an all-gather over xGMI then appends all
 ranks' transitions, in global row order, to every rank's replicated device pool; the timed region
 includes the all-gather.  value = all ranks' transitions / max-over-ranks time.
+
+A plain run sets up, warms up, times ``--steps`` rollouts and prints the headline line; ``--dump-outputs DIR``
+also writes what the last timed rollout returned and appended to the pool.  ``--full`` adds every secondary
+measurement after the timed region (per-kernel roofline, SAC, BNN.train, other configs / dtypes, CPU baselines).
 """
 import argparse
 import json
@@ -76,6 +80,13 @@ def parse():
     p.add_argument('--warmup', type=int, default=10, help='untimed rollouts first (the clocks ramp up over ~20 ms)')
     p.add_argument('--batch', type=int, default=50000)
     p.add_argument('--horizon', type=int, default=5)
+    p.add_argument('--full', action='store_true',
+                   help='after the timed steps also run every secondary measurement: per-kernel averages and the '
+                        'roofline, SAC, BNN.train, the other configs and dtypes, the CPU baselines (minutes); without '
+                        'it the run sets up, warms up, times --steps rollouts and prints the headline line')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help='write what the last timed step returned and appended to the model pool as DIR/<name>.npy '
+                        '(float32 / float64, at most 64 MB; a fixed seeded sample of the rows beyond that)')
     p.add_argument('--no-cpu-baseline', action='store_true')
     p.add_argument('--cpu-batch', type=int, default=10000,
                    help='rows of the C2 CPU-baseline rollout sample (the headline workload at fewer rows, labelled '
@@ -596,6 +607,17 @@ def main():
         torch.distributed.barrier()
     dt = time.perf_counter() - t0
     total = int(sum(int(x.sum().item()) for x in steps_t))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, steps_t[-1], pool)
+    if not args.full:   # the plain run: the headline figure only
+        if world > 1:
+            t = torch.tensor([dt], dtype=torch.float64, device=dev)
+            torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+            dt = float(t.item())
+            torch.distributed.destroy_process_group()
+        if rank == 0:
+            print(json.dumps(headline(args, world, total, dt)))
+        return
     # per-kernel durations (HIP events on the rollout's stream around every launch) come from extra,
     # untimed rollouts: the event records themselves would add gaps to the timed region
     kernel_ms, _ = kernel_profile(args, ro, pool, pi, env, staging, args.warmup + args.steps, rank, world,
@@ -622,20 +644,8 @@ def main():
         if world > 1:
             torch.distributed.destroy_process_group()
         return
-    value = total / dt
-    spec = CONFIGS[args.config]
-    out = {
-        'metric': 'model-rollout transitions/s (halfcheetah-mixed)' if args.config == 'C2' else
-                  'model-rollout transitions/s (%s: %s)' % (args.config, spec['name']),
-        'value': value, 'unit': 'transitions/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-        'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-        'dtype': dtype_desc(args.ensemble_dtype, args.actor_dtype), 'data': 'synthetic (random-init weights, N(0,1) env pool; D4RL/.mat unavailable offline)',
-        'config': {'workload': '%s rollout: E=%d (5 elites), H=%d smv, obs=17, act=6, rollout_batch=%d per GPU, '
-                               'horizon=%d, penalty_coeff=%g, learned-var penalty, env pool %d rows'
-                               % (args.config, spec['E'], spec['H'], args.batch, args.horizon, spec['penalty'],
-                                  spec['env_rows']),
-                   'rollout_batch_per_gpu': args.batch, 'horizon': args.horizon, 'parallelism': 'dp%d' % world},
-        'product_default_dtype': DEFAULT_ENSEMBLE_DTYPE,   # what MOPO.train / `mopo run_local` run
+    out = headline(args, world, total, dt)
+    out.update({
         'roofline': leg_roofline(args, kernel_ms),
         'kernel_ms_avg': kernel_ms,
         'sac': {'metric': 'SAC grad-steps/s (batch 256 = 12 env + 244 model rows, mopo.py:801-850)',
@@ -643,7 +653,7 @@ def main():
                 'us_per_step': 1e6 / sac_rate, **SAC_DIAG,
                 'parallelism': 'replicated on every rank (the same updates on identical pools; SURVEY 8(e))',
                 'roofline': sac_roofline(sac_rate)},
-    }
+    })
     if extra:
         out['extra_configs'] = extra
     if alts:
@@ -660,6 +670,46 @@ def main():
     print(json.dumps(compact_line(out)))
     if world > 1:
         torch.distributed.destroy_process_group()
+
+
+def headline(args, world, total, dt):
+    """The result line of the timed steps alone: ``total`` transitions in ``dt`` seconds (max over ranks)."""
+    value = total / dt
+    spec = CONFIGS[args.config]
+    return {
+        'metric': 'model-rollout transitions/s (halfcheetah-mixed)' if args.config == 'C2' else
+                  'model-rollout transitions/s (%s: %s)' % (args.config, spec['name']),
+        'value': value, 'unit': 'transitions/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+        'ms_per_step': dt / args.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
+        'dtype': dtype_desc(args.ensemble_dtype, args.actor_dtype), 'data': 'synthetic (random-init weights, N(0,1) env pool; D4RL/.mat unavailable offline)',
+        'config': {'workload': '%s rollout: E=%d (5 elites), H=%d smv, obs=17, act=6, rollout_batch=%d per GPU, '
+                               'horizon=%d, penalty_coeff=%g, learned-var penalty, env pool %d rows'
+                               % (args.config, spec['E'], spec['H'], args.batch, args.horizon, spec['penalty'],
+                                  spec['env_rows']),
+                   'rollout_batch_per_gpu': args.batch, 'horizon': args.horizon, 'parallelism': 'dp%d' % world},
+        'product_default_dtype': DEFAULT_ENSEMBLE_DTYPE,   # what MOPO.train / `mopo run_local` run
+    }
+
+
+DUMP_LIMIT = 64 * 1000 * 1000   # bytes --dump-outputs may write in all
+
+
+def dump_outputs(path, steps, pool):
+    """What the last timed ``_rollout_model`` gave its caller: the rows added per horizon step (float64) and the
+    transitions it appended to the model pool, field by field in append order (float32; terminals as 0 / 1).
+    Past DUMP_LIMIT bytes a fixed, seeded sample of the rows is kept, in append order."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n = min(int(steps.sum().item()), pool._max_size)
+    rows = (pool._pointer - n + np.arange(n, dtype=np.int64)) % pool._max_size   # the ring's last n rows
+    width = sum(int(v.shape[1]) for v in pool.fields.values())
+    keep = (DUMP_LIMIT - 8192) // (4 * width)   # 8192: the .npy headers and steps_added
+    if n > keep:
+        rows = rows[np.sort(np.random.RandomState(0).choice(n, keep, replace=False))]
+    np.save(os.path.join(path, 'steps_added.npy'), steps.cpu().numpy().astype(np.float64))
+    idx = torch.from_numpy(rows).to(steps.device)
+    for k, v in pool.fields.items():
+        np.save(os.path.join(path, k + '.npy'), v[idx].cpu().numpy().astype(np.float32))
 
 
 LINE_LIMIT = 7000   # the driver keeps the last ~8 KB of stdout: the one bench line must fit in it whole

@@ -11,7 +11,7 @@ TAG=${TAG:-r06}
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-NOX="--no-cpu-baseline --no-c3 --no-alt-dtypes"
+NOX="--full --no-cpu-baseline --no-c3 --no-alt-dtypes"
 declare -A A
 A[C2_f16x3]="--ensemble-dtype f16x3 --train-epochs 0 --sac-steps 16"
 A[C2_bf16x6]="--ensemble-dtype bf16x6 --train-epochs 2"

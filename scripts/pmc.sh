@@ -9,7 +9,7 @@ OUT=${1:-gpurun_out/pmc_summary.json}
 shift
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-ARGS="--steps 3 --warmup 1 --no-cpu-baseline --sac-steps 50 --no-c3 --no-alt-dtypes --train-epochs 0 --prof-steps 2 $*"
+ARGS="--full --steps 3 --warmup 1 --no-cpu-baseline --sac-steps 50 --no-c3 --no-alt-dtypes --train-epochs 0 --prof-steps 2 $*"
 KEY=$(python -c "import sys; sys.argv=['bench.py'] + sys.argv[1:]; import bench; print(bench.workload_key(bench.parse()))" $ARGS)
 TAG=$(echo "$KEY" | tr ' =' '__')
 # one stream: every ensemble launch is the full-batch launch bench.py prices (roofline.avg_launch_ms)

@@ -325,7 +325,28 @@ def sac_case(refs, name, O, A, H, n, seed, steps=3, term_frac=0.2, compact=False
             out['b%d_log_alpha_%s' % (k, tag)] = state['log_alpha:0']
             used = tfstub.S.noise_used
             assert len(used) == 4
-    np.savez_compressed(os.path.join(HERE, 'ref_sac_%s.npz' % name), **out)
+    save_split(os.path.join(HERE, 'ref_sac_%s.npz' % name), out)
+
+
+PART_BYTES = 900000   # array bytes per committed file (every file stays below 1 MiB)
+
+
+def save_split(path, out):
+    """``np.savez_compressed`` of a case; past PART_BYTES of arrays the case continues, in insertion order, in
+    parts/<name>.<n>.npz (tests/test_oracle_ref.py load_case reads them back as one dict)."""
+    groups, size = [{}], 0
+    for k, v in out.items():
+        v = np.asarray(v)
+        if groups[-1] and size + v.nbytes > PART_BYTES:
+            groups.append({})
+            size = 0
+        groups[-1][k] = v
+        size += v.nbytes
+    np.savez_compressed(path, **groups[0])
+    os.makedirs(os.path.join(os.path.dirname(path), 'parts'), exist_ok=True)
+    for n, g in enumerate(groups[1:], 1):
+        np.savez_compressed(os.path.join(os.path.dirname(path), 'parts',
+                                         '%s.%d.npz' % (os.path.basename(path)[:-4], n)), **g)
 
 
 def bnn_save_case(refs, E=3, H=32, seed=41, smv=True, dirname='ref_save'):

@@ -18,7 +18,7 @@ import os
 import numpy as np
 import pytest
 
-from test_oracle_ref import ref_bnn_params
+from test_oracle_ref import load_case, ref_bnn_params
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), 'golden')
@@ -84,7 +84,7 @@ def _pools_for_batch(b, n_env, O, A):
 def test_sac_steps_vs_reference_graph(path):
     """MOPO._do_training + _update_target (mopo.py:834-853) for consecutive steps, injected batch and
     policy noise (the 1st and 3rd tf.random_normal draws of _build: main(s) and main(s'))."""
-    z = dict(np.load(path))
+    z = load_case(path)
     O, A, n, steps = int(z['O']), int(z['A']), int(z['n']), int(z['steps'])
     sac = _sac_for_case(z)
     lr_t = [3e-4 * np.sqrt(1 - 0.999 ** (k + 1)) / (1 - 0.9 ** (k + 1)) for k in range(steps)]
@@ -130,7 +130,7 @@ def test_actor_vs_reference_graph(path, dtype):
     """get_action_meta (mopo.py:468-485): pi and the deterministic mu for the step-0 batch."""
     import torch
     from mopo_amd import _lib as L
-    z = dict(np.load(path))
+    z = load_case(path)
     O, A, H, n = int(z['O']), int(z['A']), int(z['H']), int(z['n'])
     flat = np.concatenate([z['init%d' % i].ravel() for i in range(20)]).astype(np.float32)
     dev = torch.device('cuda')
@@ -150,7 +150,7 @@ def test_softlearning_sac_api_vs_reference_graph():
     _do_training(iteration, batch) with a batch dict: step 0 of the reference-executed H=256 case."""
     import types
     from mopo_amd.sac import SAC
-    z = dict(np.load(os.path.join(GOLD, 'ref_sac_H256.npz')))
+    z = load_case(os.path.join(GOLD, 'ref_sac_H256.npz'))
     O, A, H, n = int(z['O']), int(z['A']), int(z['H']), int(z['n'])
     env = types.SimpleNamespace(observation_space=types.SimpleNamespace(shape=(O,)),
                                 action_space=types.SimpleNamespace(shape=(A,)))

@@ -23,6 +23,16 @@ SAC_KEYS = ('Q/q1_loss', 'sac_Q/q2_loss', 'sac_Q/q1', 'sac_Q/q2', 'sac_pi/alpha'
             'sac_pi/pi_entropy', 'sac_pi/std', 'sac_pi/pi_global_norm', 'sac_Q/q_global_norm')
 
 
+def load_case(path):
+    """A reference case as one dict: <name>.npz plus, for a case too large for one committed file, its
+    continuation golden/parts/<name>.<n>.npz (written by make_ref_vectors.py save_split)."""
+    z = dict(np.load(path))
+    stem = os.path.basename(path)[:-len('.npz')]
+    for part in sorted(glob.glob(os.path.join(os.path.dirname(path), 'parts', stem + '.*.npz'))):
+        z.update(np.load(part))
+    return z
+
+
 def rel(a, b):
     return float(np.max(np.abs(np.asarray(a, np.float64) - b) / (1e-30 + np.abs(b)))) if np.size(b) else 0.0
 
@@ -100,7 +110,7 @@ def _sac_batch(z, k):
 @pytest.mark.parametrize('path', SAC, ids=[os.path.basename(p) for p in SAC])
 def test_sac_oracle_vs_reference_graph(path):
     """MOPO._build / _do_training / _update_target executed from the reference, several steps."""
-    z = dict(np.load(path))
+    z = load_case(path)
     steps = int(z['steps'])
     st = osac.SACState([z['init%d' % i].astype(np.float64) for i in range(20)])
     for k in range(steps):
@@ -130,7 +140,7 @@ def test_sac_polyak_pairing_from_reference_graph():
     """zip(get_vars('main'), get_vars('target')) (mopo.py:446-447) pairs each target with its own
     main variable, the Adam slots excluded by truncation: the recorded assigns are exactly
     target <- 0.995 target + 0.005 main, in creation order."""
-    z = dict(np.load(SAC[0]))
+    z = load_case(SAC[0])
     pairs = [str(p) for p in z['polyak_pairs']]
     assert len(pairs) == 40
     for i in range(20):
@@ -147,7 +157,7 @@ def test_sac_polyak_pairing_from_reference_graph():
 def test_actor_oracle_vs_reference_graph():
     """get_action_meta (mopo.py:468-485) on the step-0 batch with the first tf.random_normal draw."""
     for path in SAC:
-        z = dict(np.load(path))
+        z = load_case(path)
         P = osac.split([z['init%d' % i].astype(np.float64) for i in range(20)])[0]
         a, mu = osac.actor_act(P, z['b0_observations'].astype(np.float64), z['b0_noise0'][0].astype(np.float64))
         np.testing.assert_allclose(a, z['actor_pi_f64'], rtol=0, atol=1e-12)
