@@ -924,6 +924,9 @@ __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_
   static_assert(P == 1 || P == 2 || P == 3, "1: bf16, 2: f16x3, 3: bf16x6 (the exact 3-part bf16 split)");
   static_assert(DEPTH >= 3, "ring of at least 3 slots");
   constexpr bool F16 = P == 2;
+  // the ring copies go out as buffer_load ... lds: they stay in flight under the fragment reads, and behind
+  // the FLAT form hipcc waits for every LDS read with lgkmcnt(0) (mlp_tile.h copy_lds16)
+  constexpr bool RBUF = true;
   // the head's slices carry HPS weight parts each: all P of a k-group where they fit a hidden layer's slot
   // (its P NBO fragments are contiguous in the packing), so the narrow head runs behind KG barriers, not P KG
   constexpr int HPS = BNN_RING_HEAD_MERGE && Stage<P * NBO, WAVES>::SLOTS <= Stage<NB2, WAVES>::SLOTS ? P : 1;
@@ -965,7 +968,11 @@ __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_
       constexpr int L = J < P ? 0 : 1 + (J - P) / (P * KG);
       constexpr int NF = L == 4 ? HPS * NBO : NB2;
       constexpr int s = J - (L == 0 ? 0 : P + P * KG * (L - 1));
-      stage_slice<NF, WAVES>(src[L] + s * NF * 256, lds + (J % DEPTH) * SLOT, wv, lane);
+      constexpr int NFU = L == 4 ? HPS * NBO : NBU;   // the slice's used fragments (its first NFU)
+      if constexpr (WAVES == 4 && NFU % 4 == 1)   // 13 of 14 (H = 200), the 9-fragment head: no pad copies
+        stage_slice_quarters<NFU, WAVES, RBUF>(src[L] + s * NF * 256, lds + (J % DEPTH) * SLOT, wv, lane);
+      else
+        stage_slice<NF, WAVES, RBUF>(src[L] + s * NF * 256, lds + (J % DEPTH) * SLOT, wv, lane);
     }
   };
   const int64_t bs = w.BS;
@@ -1010,7 +1017,7 @@ __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_
   // for the copies too: vmcnt is in order)
   wait_vm_lgkm0<0>();
   __builtin_amdgcn_sched_barrier(0);
-  stage_bias<NB2 * 4, WAVES>(w.b0 + e * bs, lds_bias0, wv, lane);   // layer 0's bias (slot 0), ahead of every slice
+  stage_bias<NB2 * 4, WAVES, RBUF>(w.b0 + e * bs, lds_bias0, wv, lane);   // layer 0's bias (slot 0), ahead of every slice
   RingRun<0, DEPTH - 1>::run([&](auto jc) { issue(jc); });
 
   constexpr float kNegLog2e = -1.4426950408889634f, kNegLn2 = -0.6931471805599453f;
@@ -1125,7 +1132,7 @@ __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_
       // the next layer's bias into slot (L + 1) & 1: every wave is past layer L - 1's epilogue, the last
       // reader of that slot
       if constexpr (s == 0 && L < 3)
-        stage_bias<NB2 * 4, WAVES>(w.bh + ((int64_t)L * E + e) * bs, lds_bias0 + ((L + 1) & 1) * BIAS_LDS, wv, lane);
+        stage_bias<NB2 * 4, WAVES, RBUF>(w.bh + ((int64_t)L * E + e) * bs, lds_bias0 + ((L + 1) & 1) * BIAS_LDS, wv, lane);
       issue(std::integral_constant<int, J + DEPTH - 1>{});
       __builtin_amdgcn_sched_barrier(0);
       const float* b = lds + (J % DEPTH) * SLOT;

@@ -50,24 +50,25 @@ struct Stage {
   static constexpr int SLOTS = PER * WAVES;
 };
 
-// One wave-wide 16-B-per-lane copy HBM -> LDS (lane l's quad lands at lds + 4 l): global_load_lds with a
-// 64-bit per-lane address (one v_lshl_add_u64 per copy).  MOPO_LDS_BUF = 1 issues it as buffer_load ...
-// lds with the wave-uniform part of the address in SGPRs (descriptor + soffset) and only lane * 16 in a
-// VGPR -- no VALU per copy, but measured 5 % slower on the headline rollout (same-box A/B: 122.7 vs
-// 129.2M transitions/s, ensemble 0.347 vs 0.333 ms), so it stays off.
-#ifndef MOPO_LDS_BUF
-#define MOPO_LDS_BUF 0
-#endif
+// One wave-wide 16-B-per-lane copy HBM -> LDS (lane l's quad lands at lds + 4 l).  BUF = false: global_load_lds
+// with a 64-bit per-lane address (one v_lshl_add_u64 per copy).  BUF = true: buffer_load ... lds (MUBUF) with the
+// wave-uniform part of the address in SGPRs (descriptor + soffset; `base` must be wave-uniform) and only
+// lane * 16 in a VGPR.  The two land the same bytes; they differ in how hipcc waits for LDS READS issued while
+// copies are in flight: behind a pending global_load_lds (FLAT encoding) every ds_read dependency is waited for
+// with lgkmcnt(0), behind the MUBUF form with a counted lgkmcnt(N).  Kernels that drain their copies at a
+// __syncthreads() before they read LDS get counted waits either way and keep the FLAT form; the ring kernel
+// (bnn.hip), which computes under copies in flight, takes BUF = true.
+template <bool BUF = false>
 __device__ __forceinline__ void copy_lds16(const float* __restrict__ base, int lane_quad, int uni_quads, float* lds) {
-#if MOPO_LDS_BUF
-  const auto r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, 0x7fffffff, 0x00020000);
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_t)lds, 16, lane_quad * 16, uni_quads * 16, 0, 0);
-#else
-  __builtin_amdgcn_global_load_lds((const void*)(base + (uni_quads + lane_quad) * 4), (lds_void_t)lds, 16, 0, 0);
-#endif
+  if constexpr (BUF) {
+    const auto r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, 0x7fffffff, 0x00020000);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_t)lds, 16, lane_quad * 16, uni_quads * 16, 0, 0);
+  } else {
+    __builtin_amdgcn_global_load_lds((const void*)(base + (uni_quads + lane_quad) * 4), (lds_void_t)lds, 16, 0, 0);
+  }
 }
 
-template <int NB, int WAVES>
+template <int NB, int WAVES, bool BUF = false>
 __device__ __forceinline__ void stage_slice(const float* __restrict__ src, float* lds, int w, int lane) {
 #pragma unroll
   for (int i = 0; i < Stage<NB, WAVES>::PER; ++i) {
@@ -75,21 +76,46 @@ __device__ __forceinline__ void stage_slice(const float* __restrict__ src, float
 // pad slots re-read a valid fragment (never consumed); measured: skipping them with a wave-uniform
     // branch is ~1.5 % slower for H = 200 (13 of 16 slots used)
     const int fs = f < NB ? f : NB - 1;
-    copy_lds16(src, lane, fs * 64, lds + f * 256);
+    copy_lds16<BUF>(src, lane, fs * 64, lds + f * 256);
   }
+}
+
+// One wave-wide 4-B-per-lane copy (256 B; lane l's dword lands at lds + l), as copy_lds16
+template <bool BUF = false>
+__device__ __forceinline__ void copy_lds4(const float* __restrict__ base, int lane, int uni_dwords, float* lds) {
+  if constexpr (BUF) {
+    const auto r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, 0x7fffffff, 0x00020000);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (lds_void_t)lds, 4, lane * 4, uni_dwords * 4, 0, 0);
+  } else {
+    __builtin_amdgcn_global_load_lds((const void*)(base + uni_dwords + lane), (lds_void_t)lds, 4, 0, 0);
+  }
+}
+
+// stage_slice for NU = 4 k + 1 fragments and 4 waves without pad copies: k whole fragments per wave and the last
+// fragment in quarters, wave w its bytes [256 w, 256 w + 256) as one dword copy.  The same k + 1 copies per wave
+// as stage_slice (uniform vmcnt), NU KiB moved instead of 4 (k + 1).
+template <int NU, int WAVES, bool BUF = false>
+__device__ __forceinline__ void stage_slice_quarters(const float* __restrict__ src, float* lds, int w, int lane) {
+  static_assert(WAVES == 4 && NU % WAVES == 1, "4 waves, 4 k + 1 fragments");
+#pragma unroll
+  for (int i = 0; i < NU / WAVES; ++i) {
+    const int f = w + i * WAVES;
+    copy_lds16<BUF>(src, lane, f * 64, lds + f * 256);
+  }
+  copy_lds4<BUF>(src, lane, (NU - 1) * 256 + w * 64, lds + (NU - 1) * 256 + w * 64);
 }
 
 // acc[r][nb] = sum over KG k-groups of W(kg, nb) x in[r][kg]; wf = this member's layer fragments.
 // If `bias` is given, the layer's BQ*4 bias values (default NB*16) are copied to lds_bias (1 KiB global_load_lds
 // pieces, one per wave) together with the last k-group's slice, so the barrier that publishes that slice
 // also publishes the bias for the epilogue (bias_swish reads it from LDS).
-template <int BQ, int WAVES>
+template <int BQ, int WAVES, bool BUF = false>
 __device__ __forceinline__ void stage_bias(const float* __restrict__ bias, float* lds_bias, int w, int lane) {
   constexpr int PIECES = (BQ + 63) / 64;  // BQ quads; 1 KiB (64 quads) per wave-wide copy
   static_assert(PIECES <= WAVES, "bias larger than one copy per wave");
   if (w < PIECES) {
     const int q = min(w * 64 + lane, BQ - 1);
-    copy_lds16(bias, q, 0, lds_bias + w * 256);
+    copy_lds16<BUF>(bias, q, 0, lds_bias + w * 256);
   }
 }
 

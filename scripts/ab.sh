@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
 : > gpurun_out/ab.txt
-for i in 1 2 3; do
+for i in $(seq ${ROUNDS:-3}); do
   for v in ${AB:-new old}; do
     so=${v%%:*}; envs=""; [ "$so" != "$v" ] && envs=${v#*:}
     cp abv/$so.so mopo_amd/libmopo_hip.so
