@@ -51,9 +51,12 @@ typedef struct mopo_bnn_s* mopo_bnn_t;
  *        4 = "f16x3": every f32 operand as 2 fp16 parts under power-of-two scales (per weight block,
  *            per activation row), 3 f16 products per f32 product, f32 accumulate (~22-bit operands,
  *            held to the fp32 parity tolerances; MOPO's default and the bench headline).
- * Limits: obs_dim + act_dim <= 32 (one or two 16-wide input k-groups); hidden 32, 64, 200 or 400 (any
- * width with the same number of 16-wide blocks); the bf16 kinds need 2 (obs_dim + 1) <= 48 head
- * slots; E <= 256. */
+ * Limits: obs_dim + act_dim <= 64 and obs_dim <= 31 (refused here otherwise); hidden 32, 64, 200 or 400
+ * (any width with the same number of 16-wide blocks); E <= 256.  Up to 32 inputs and obs_dim <= 23 (one
+ * or two 16-wide input k-groups, at most 48 head slots) every dtype runs.  Wider models (e.g. ant's
+ * 27 + 8) run one padded form, 64 input slots and 64 head slots: fp32 at every hidden size, bf16x6 and
+ * f16x3 at hidden 32, 64 and 200 only (so e.g. hidden 33..48 or 400 with a 16-bit dtype, and bf16 / bf16x3
+ * at any width, are refused here on a wide shape, with a message naming what runs). */
 int mopo_bnn_create(mopo_bnn_t* out, int E, int obs_dim, int act_dim, int hidden, int smv, int dtype);
 int mopo_bnn_destroy(mopo_bnn_t h);
 /* The reference .mat layout, keys '0'..'15' (bnn.py:224-225, 588-592): mu[1,IN], sigma[1,IN],

@@ -26,6 +26,11 @@
 
 namespace mopo {
 
+static const char* const kWide16Msg =
+    "bnn: a wide model (obs_dim + act_dim > 32 or obs_dim > 23) runs in fp32 at hidden 32, 64, 200 or 400 and in "
+    "bf16x6 / f16x3 at hidden 32, 64 or 200 (the widths with the same number of 16-wide blocks); bf16, bf16x3 and "
+    "other hidden sizes are not supported there";
+
 // ---------------------------------------------------------------------------------------
 // weight packing:  src W[E][K][N] (TF layout, x @ W)  ->  fragment-major (see internal.h);
 // perm_k / perm_n: that side is a hidden/input width laid out by slot_feat (mlp_tile.h)
@@ -236,7 +241,8 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES >= 8 || NBH > 16) ? BNN_MINB_WID
     for (int r = 0; r < R; ++r) {
       const int64_t row = row0 + r * 16 + m;
 #pragma unroll
-      for (int kg = 0; kg < KG0; ++kg) x0[r][kg] = row < count ? ld4(a.xs + row * XS_STRIDE + kg * 16 + 4 * g) : zero4();
+      for (int kg = 0; kg < KG0; ++kg)
+        x0[r][kg] = row < count ? ld4(a.xs + row * (KG0 > 2 ? XS_STRIDE_WIDE : XS_STRIDE) + kg * 16 + 4 * g) : zero4();
     }
   } else
 #pragma unroll
@@ -917,7 +923,9 @@ __global__ __launch_bounds__(WAVES * 64, R == 1 ? 2 : 1) void bnn_fwd_f16r_kerne
 #ifndef BNN_RING_MINB_X6
 #define BNN_RING_MINB_X6 3  // the same for bf16x6 (P = 3)
 #endif
-template <int NB2, int NBO, int MODE, int WAVES, int P, int DEPTH, int NBU = NB2>
+// KG0B: 32-deep k-groups of the input row (2: wide models, up to 64 inputs; layer 0 then owns P KG0B slices,
+// w0b is [E][KG0B][P][NB2] and the xs rows lie 32 KG0B floats apart)
+template <int NB2, int NBO, int MODE, int WAVES, int P, int DEPTH, int NBU = NB2, int KG0B = 1>
 __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_MINB) * 4 / WAVES > 0)
                                              ? (P == 3 ? BNN_RING_MINB_X6 : BNN_RING_MINB) * 4 / WAVES : 1) void bnn_fwd_ring_kernel(const BnnDev w,
                                                                                             const FwdArgs a) {
@@ -930,8 +938,9 @@ __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_
   // the head's slices carry HPS weight parts each: all P of a k-group where they fit a hidden layer's slot
   // (its P NBO fragments are contiguous in the packing), so the narrow head runs behind KG barriers, not P KG
   constexpr int HPS = BNN_RING_HEAD_MERGE && Stage<P * NBO, WAVES>::SLOTS <= Stage<NB2, WAVES>::SLOTS ? P : 1;
-  constexpr int KG = NB2 / 2, NS = P + 3 * KG * P + KG * (P / HPS);
-  constexpr int JHEAD = P + 3 * KG * P;  // the head's first slice
+  constexpr int P0 = P * KG0B;   // layer 0's slices
+  constexpr int KG = NB2 / 2, NS = P0 + 3 * KG * P + KG * (P / HPS);
+  constexpr int JHEAD = P0 + 3 * KG * P;  // the head's first slice
   constexpr bool KH = NBU < NB2;
   constexpr int SLOT = Stage<(NB2 > HPS * NBO ? NB2 : HPS * NBO), WAVES>::SLOTS * 256;
   constexpr int BIAS_LDS = (NB2 * 4 + 63) / 64 * 256;
@@ -956,18 +965,18 @@ __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_
     mx = fmaxf(mx, __shfl_xor(mx, 16));
     return fmaxf(mx, __shfl_xor(mx, 32));
   };
-  // slice stream: layer L (0 input, 1..3 hidden, 4 head) owns slices [P + P KG (L - 1), ...) (layer 0: [0, P))
+  // slice stream: layer L (0 input, 1..3 hidden, 4 head) owns slices [P0 + P KG (L - 1), ...) (layer 0: [0, P0))
   const float* src[5];
-  src[0] = w.w0b + (int64_t)e * P * NB2 * 256;
+  src[0] = w.w0b + (int64_t)e * P0 * NB2 * 256;
 #pragma unroll
   for (int l = 0; l < 3; ++l) src[1 + l] = w.whb + ((int64_t)l * E + e) * KG * P * NB2 * 256;
   src[4] = w.whdb + (int64_t)e * KG * P * NBO * 256;
   auto issue = [&](auto jc) {  // every wave's copies of slice J (PER per wave, pads re-read a fragment)
     constexpr int J = decltype(jc)::value;
     if constexpr (J < NS) {
-      constexpr int L = J < P ? 0 : 1 + (J - P) / (P * KG);
+      constexpr int L = J < P0 ? 0 : 1 + (J - P0) / (P * KG);
       constexpr int NF = L == 4 ? HPS * NBO : NB2;
-      constexpr int s = J - (L == 0 ? 0 : P + P * KG * (L - 1));
+      constexpr int s = J - (L == 0 ? 0 : P0 + P * KG * (L - 1));
       constexpr int NFU = L == 4 ? HPS * NBO : NBU;   // the slice's used fragments (its first NFU)
       if constexpr (WAVES == 4 && NFU % 4 == 1)   // 13 of 14 (H = 200), the 9-fragment head: no pad copies
         stage_slice_quarters<NFU, WAVES, RBUF>(src[L] + s * NF * 256, lds + (J % DEPTH) * SLOT, wv, lane);
@@ -977,27 +986,32 @@ __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_
   };
   const int64_t bs = w.BS;
 
-  float xv[8];
+  float xv[KG0B][8];
   if (a.xs) {  // rollout: the actor already wrote the scaled row in slot order (bf16_kperm)
-    const f32x4 lo = ok ? ld4(a.xs + row * XS_STRIDE + 4 * g) : zero4();
-    const f32x4 hi = ok ? ld4(a.xs + row * XS_STRIDE + 16 + 4 * g) : zero4();
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      xv[t] = lo[t];
-      xv[4 + t] = hi[t];
+    for (int c = 0; c < KG0B; ++c) {
+      const f32x4 lo = ok ? ld4(a.xs + row * (XS_STRIDE * KG0B) + 32 * c + 4 * g) : zero4();
+      const f32x4 hi = ok ? ld4(a.xs + row * (XS_STRIDE * KG0B) + 32 * c + 16 + 4 * g) : zero4();
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        xv[c][t] = lo[t];
+        xv[c][4 + t] = hi[t];
+      }
     }
   } else {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int k = slot_feat(bf16_kperm(g, j), IN);
-      float v = 0.f;
-      if (ok && k >= 0) {
-        float raw = k < O ? load_feat(a.in.xa, a.in.xa_f64, row * a.in.sa + k)
-                          : load_feat(a.in.xb, a.in.xb_f64, row * a.in.sb + (k - O));
-        v = (raw - w.mu[k]) / w.sigma[k];
+    for (int c = 0; c < KG0B; ++c)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int k = slot_feat(32 * c + bf16_kperm(g, j), IN);
+        float v = 0.f;
+        if (ok && k >= 0) {
+          float raw = k < O ? load_feat(a.in.xa, a.in.xa_f64, row * a.in.sa + k)
+                            : load_feat(a.in.xb, a.in.xb_f64, row * a.in.sb + (k - O));
+          v = (raw - w.mu[k]) / w.sigma[k];
+        }
+        xv[c][j] = v;
       }
-      xv[j] = v;
-    }
   }
   // f16x3: the five layers' weight scales, loaded with the row and kept in SGPRs (a vector load of one
   // later would be waited for with vmcnt(0), draining the slices in flight); the input row's scale
@@ -1010,7 +1024,9 @@ __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_
     for (int l = 0; l < 5; ++l) wsc[l] = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(wsc[l])));
     float mx0 = 0.f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) mx0 = fmaxf(mx0, fabsf(xv[j]));
+    for (int c = 0; c < KG0B; ++c)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) mx0 = fmaxf(mx0, fabsf(xv[c][j]));
     row_scale(row_max(mx0), s_in, inv_row);
   }
   // the row is in registers before the first copies go out (a later first use of its loads would wait
@@ -1104,10 +1120,10 @@ __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_
   // layer L: NBL output blocks (NBUL used), KGL k-groups of input `in`, slices [J0, J0 + P KGL)
   auto layer = [&](auto Lc, auto& in) {
     constexpr int L = decltype(Lc)::value;
-    constexpr int KGL = L == 0 ? 1 : KG, NBL = L == 4 ? NBO : NB2, NBUL = L == 4 ? NBO : NBU;
+    constexpr int KGL = L == 0 ? KG0B : KG, NBL = L == 4 ? NBO : NB2, NBUL = L == 4 ? NBO : NBU;
     constexpr bool KHL = L > 0 && KH;
     constexpr bool DEFER = DEF && L > 0;   // `in` holds u; y' made one k-group ahead
-    constexpr int J0 = L == 0 ? 0 : P + P * KG * (L - 1);
+    constexpr int J0 = L == 0 ? 0 : P0 + P * KG * (L - 1);
     constexpr int PPS = L == 4 ? HPS : 1, SPK = P / PPS;   // weight parts per slice, slices per k-group
 #pragma unroll
     for (int nb = 0; nb < NBL; ++nb) acc[nb] = zero4();
@@ -1169,9 +1185,11 @@ __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_
     });
   };
   {
-    float x1[1][8];
+    float x1[KG0B][8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) x1[0][j] = xv[j];
+    for (int c = 0; c < KG0B; ++c)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) x1[c][j] = xv[c][j];
     layer(std::integral_constant<int, 0>{}, x1);
   }
   to_input(inv_row * wsc[0] * kNegLog2e);  // layer 0's input is x itself
@@ -1199,7 +1217,7 @@ __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_
                            (MODE == FWD_ROLLOUT && a.sel && ok_e) ? a.sel[row_e] : -1);
 }
 
-template <int NB2, int NBO, int P, int DEPTH>
+template <int NB2, int NBO, int P, int DEPTH, int KG0B = 1>
 static int launch_ring(const Bnn* h, int mode, FwdArgs a, hipStream_t s) {
   constexpr int WV = BNN_RING_WAVES;
   a.ntiles = (int)ceil_div((int)a.B, 16);
@@ -1209,9 +1227,9 @@ static int launch_ring(const Bnn* h, int mode, FwdArgs a, hipStream_t s) {
   // whole-block NB2 = 14 form (H = 209..224, no config) is not instantiated (it spilled 8-12 B)
   constexpr int NBU = NB2 == 14 ? NB2 - 1 : NB2;
   if (mode == FWD_PREDICT) {
-    hipLaunchKernelGGL((bnn_fwd_ring_kernel<NB2, NBO, FWD_PREDICT, WV, P, DEPTH, NBU>), grid, block, 0, s, h->dev, a);
+    hipLaunchKernelGGL((bnn_fwd_ring_kernel<NB2, NBO, FWD_PREDICT, WV, P, DEPTH, NBU, KG0B>), grid, block, 0, s, h->dev, a);
   } else {
-    hipLaunchKernelGGL((bnn_fwd_ring_kernel<NB2, NBO, FWD_ROLLOUT, WV, P, DEPTH, NBU>), grid, block, 0, s, h->dev, a);
+    hipLaunchKernelGGL((bnn_fwd_ring_kernel<NB2, NBO, FWD_ROLLOUT, WV, P, DEPTH, NBU, KG0B>), grid, block, 0, s, h->dev, a);
   }
   MOPO_HIP(hipGetLastError());
   return 0;
@@ -1249,11 +1267,13 @@ static int launch_fwd_h(const Bnn* h, int mode, const FwdArgs& a, hipStream_t s)
     case 2: return launch_fwd_t<KG0, 2, NBO, 2>(h, mode, a, s);
     case 4: return launch_fwd_t<KG0, 4, NBO, 2>(h, mode, a, s);
     case 13:  // H = 200 with 17 + 6 inputs (every halfcheetah / walker2d config): skip the padding k-steps
-      if (KG0 == 2 && NBO == 3 && tail_steps(h->dev.IN) <= 2 && tail_steps(h->H) <= 2)
-        return launch_fwd_t<KG0, 13, NBO, BNN_R13, 2, 2>(h, mode, a, s);
+      if constexpr (KG0 <= 2)   // the wide form (KG0 = 4) has the whole-k-group variant only
+        if (KG0 == 2 && NBO == 3 && tail_steps(h->dev.IN) <= 2 && tail_steps(h->H) <= 2)
+          return launch_fwd_t<KG0, 13, NBO, BNN_R13, 2, 2>(h, mode, a, s);
       return launch_fwd_t<KG0, 13, NBO, BNN_R13>(h, mode, a, s);
     case 25:
-      if (KG0 == 2 && NBO == 3 && tail_steps(h->dev.IN) <= 2) return launch_fwd_t<KG0, 25, NBO, 1, 2, 4>(h, mode, a, s);
+      if constexpr (KG0 <= 2)
+        if (KG0 == 2 && NBO == 3 && tail_steps(h->dev.IN) <= 2) return launch_fwd_t<KG0, 25, NBO, 1, 2, 4>(h, mode, a, s);
       return launch_fwd_t<KG0, 25, NBO, 1>(h, mode, a, s);
   }
   return fail("bnn: unsupported hidden size (supported: 32, 64, 200, 400; got H=" +
@@ -1391,8 +1411,24 @@ static int launch_bf16_t(const Bnn* h, int mode, const FwdArgs& a, hipStream_t s
   return launch_bf16_p<NB2, NBO, 1>(h, mode, a, s);
 }
 
+// wide models (bnn_wide: 2 input k-groups of 32, 4 head blocks) on the ring kernel: bf16x6 and f16x3 at H = 32, 64, 200
+template <int NB2>
+static int launch_wide16(const Bnn* h, int mode, const FwdArgs& a, hipStream_t s) {
+  if (!ring_shape<NB2>(h)) return fail(kWide16Msg);
+  if (h->dtype == DT_F16X3) return launch_ring<NB2, 4, 2, BNN_RING_DEPTH_F16, 2>(h, mode, a, s);
+  if (h->dtype == DT_BF16X6) return launch_ring<NB2, 4, 3, BNN_RING_DEPTH_BF16, 2>(h, mode, a, s);
+  return fail(kWide16Msg);
+}
+
 static int launch_bf16(const Bnn* h, int mode, const FwdArgs& a, hipStream_t s) {
-  if (h->dev.IN > 32) return fail("bnn bf16: obs_dim + act_dim must be <= 32");
+  if (bnn_wide(h->dev.IN, h->dev.D)) {
+    switch (h->dev.NB2) {
+      case 2: return launch_wide16<2>(h, mode, a, s);
+      case 4: return launch_wide16<4>(h, mode, a, s);
+      case 14: return launch_wide16<14>(h, mode, a, s);
+    }
+    return fail(kWide16Msg);
+  }
   if (h->dev.NBO == 3) {
     switch (h->dev.NB2) {
       case 2: return launch_bf16_t<2, 3>(h, mode, a, s);
@@ -1412,7 +1448,9 @@ static int launch_bf16(const Bnn* h, int mode, const FwdArgs& a, hipStream_t s) 
 int launch_bnn_fwd(const Bnn* h, int mode, const FwdArgs& a, hipStream_t s) {
   if (!h->has_params) return fail("bnn: parameters not set (mopo_bnn_set_params)");
   if (h->dtype != 0) return launch_bf16(h, mode, a, s);
-  if (h->dev.KG0 != 1 && h->dev.KG0 != 2) return fail("bnn: obs_dim + act_dim must be <= 32");
+  // wide models: one form per hidden width, 4 input k-groups and 4 head blocks (unused ones are zero padding)
+  if (h->dev.KG0 == 4 && h->dev.NBO == 4) return launch_fwd_h<4, 4>(h, mode, a, s);
+  if (h->dev.KG0 != 1 && h->dev.KG0 != 2) return fail("bnn: obs_dim + act_dim must be <= 64");
   const bool k1 = h->dev.KG0 == 1;  // hopper: 11 + 3 inputs
   switch (h->dev.NBO) {
     case 3: return k1 ? launch_fwd_h<1, 3>(h, mode, a, s) : launch_fwd_h<2, 3>(h, mode, a, s);
@@ -1437,11 +1475,23 @@ extern "C" int mopo_bnn_create(mopo_bnn_t* out, int E, int obs_dim, int act_dim,
   h->E = E; h->O = obs_dim; h->A = act_dim; h->H = hidden; h->smv = smv; h->dtype = dtype;
   BnnDev& d = h->dev;
   d.E = E; d.O = obs_dim; d.A = act_dim; d.IN = obs_dim + act_dim; d.H = hidden; d.D = obs_dim + 1;
-  d.KG0 = ceil_div(d.IN, 16);
+  if (d.IN > 16 * MAX_IN_KG || d.D > 32) {
+    delete h;
+    return fail("mopo_bnn_create: obs_dim + act_dim must be <= 64 and obs_dim <= 31 (got obs_dim " +
+                std::to_string(obs_dim) + ", act_dim " + std::to_string(act_dim) + ")");
+  }
+  // wide models (more than 32 inputs or more than 3 head blocks) run one padded form: 4 input k-groups, 4 head blocks
+  const bool wide = bnn_wide(d.IN, d.D);
+  d.KG0 = wide ? MAX_IN_KG : ceil_div(d.IN, 16);
   d.NBH = ceil_div(hidden, 16);
-  d.NBO = ceil_div(2 * d.D, 16);
+  d.NBO = wide ? 4 : ceil_div(2 * d.D, 16);
   d.NB2 = (d.NBH + 1) / 2 * 2;
   d.BS = d.NB2 * 16;
+  if (wide && dtype != DT_FP32 &&
+      !((dtype == DT_BF16X6 || dtype == DT_F16X3) && ((d.NB2 == 14 && d.NBH == 13) || (d.NB2 == 4 && d.NBH == 4) || d.NBH == 2))) {
+    delete h;
+    return fail(std::string("mopo_bnn_create: ") + kWide16Msg);
+  }
   if (dtype != 0 && d.NB2 == 14 && d.NBH != 13) {   // the 16-bit kernels' NB2 = 14 shape is H = 200's 13 blocks
     delete h;
     return fail("mopo_bnn_create: the 16-bit dtypes do not support hidden sizes 209..224 (got " +
@@ -1557,9 +1607,10 @@ extern "C" int mopo_bnn_set_params(mopo_bnn_t hh, const float* const* arrs, int 
     MOPO_HIP(hipMemcpy(bhd, aux.data(), aux.size() * sizeof(float), hipMemcpyHostToDevice));
   }
   if (h->dtype != 0 && rc == 0) {
-    // bf16 fragments: [E][1][P][NB2] | [3][E][KG][P][NB2] | [E][KG][P][NBO], 256 floats (= 512 bf16) each
-    const int NB2 = d.NB2, KG = NB2 / 2, P = bf16_parts(h->dtype);
-    const int64_t f0 = (int64_t)E * P * NB2, fh = 3LL * E * KG * P * NB2, fd = (int64_t)E * KG * P * NBO;
+    // bf16 fragments: [E][KG0B][P][NB2] | [3][E][KG][P][NB2] | [E][KG][P][NBO], 256 floats (= 512 bf16) each;
+    // KG0B = the input's 32-deep k-groups: 1, wide models (KG0 = 4) 2
+    const int NB2 = d.NB2, KG = NB2 / 2, P = bf16_parts(h->dtype), KG0B = (KG0 + 1) / 2;
+    const int64_t f0 = (int64_t)E * KG0B * P * NB2, fh = 3LL * E * KG * P * NB2, fd = (int64_t)E * KG * P * NBO;
     if (!h->bbuf) MOPO_HIP(hipMalloc(&h->bbuf, (f0 + fh + fd) * 256 * sizeof(float)));
     h->bbuf_bytes = (f0 + fh + fd) * 256 * (int64_t)sizeof(float);
     float* b0f = reinterpret_cast<float*>(h->bbuf);
@@ -1605,7 +1656,7 @@ extern "C" int mopo_bnn_set_params(mopo_bnn_t hh, const float* const* arrs, int 
       ++layer_idx;
       return 0;
     };
-    if (rc == 0) rc = packh(W[0], (size_t)E * IN * H, b0f, IN, H, 1, NB2, 1);
+    if (rc == 0) rc = packh(W[0], (size_t)E * IN * H, b0f, IN, H, KG0B, NB2, 1);
     for (int l = 0; l < 3 && rc == 0; ++l)
       rc = packh(W[1 + l], (size_t)E * H * H, bhf + (int64_t)l * E * KG * P * NB2 * 256, H, H, KG, NB2, 1);
     if (rc == 0) rc = packh(head.data(), head.size(), bdf, H, 2 * D, KG, NBO, 2);

@@ -6,6 +6,10 @@
 namespace mopo {
 
 constexpr int MAX_IN_KG = 4;  // layer-0 input features <= 64
+// A "wide" ensemble has more than 32 inputs or more than 3 head blocks (D = obs_dim + 1 > 24), e.g. ant's
+// 27 + 8.  Every wide shape runs ONE padded form per hidden width: KG0 = 4 input k-groups of 16 (two of 32
+// in the 16-bit kernels) and NBO = 4 head blocks; unused slots are zero weights (slot_feat / head_col: -1).
+__host__ __device__ constexpr bool bnn_wide(int IN, int D) { return IN > 32 || D > 24; }
 
 // Device view of a packed ensemble.  Weight matrices are stored "fragment-major": for
 // layer input K (KG = ceil(K/16) k-groups) and output N (NB = ceil(N/16) blocks), member e,
@@ -29,7 +33,7 @@ struct BnnDev {
   // bf16 fragments (dtype 1..3): 1 KiB = 64 lanes x 8 bf16 per (32-deep k-group, 16-wide block),
   // addressed in float units like the f32 fragments; hidden width padded to NB2 = even(NBH)
   int NB2;
-  const float* w0b;   // [E][1][NB2]
+  const float* w0b;   // [E][KG0B][P][NB2], KG0B = (KG0 + 1) / 2 input k-groups of 32 (1; wide models 2)
   const float* whb;   // [3][E][NB2/2][NB2]
   const float* whdb;  // [E][NB2/2][NBO]
   const float* wscale;  // f16x3: [5][E] inverse power-of-two weight scales (layer 0, hidden 1..3, head)
@@ -56,13 +60,17 @@ struct FwdIn {
 
 enum { FWD_PREDICT = 0, FWD_ROLLOUT = 1 };
 constexpr int XS_STRIDE = 32;  // floats per pre-scaled input row (FwdArgs::xs): 2 k-groups of slots
+// wide models (more than 32 inputs or more than 3 head blocks: BnnDev::KG0 = 4): 4 k-groups of slots
+constexpr int XS_STRIDE_WIDE = 64;
+__host__ __device__ constexpr int xs_stride(int kg0) { return kg0 > 2 ? XS_STRIDE_WIDE : XS_STRIDE; }
 
 struct FwdArgs {
   FwdIn in;
   int64_t B;              // launch rows (grid sized for this)
   const int* d_count;     // optional device row count (<= B)
   // optional pre-scaled input rows [B][32] f32 in slot_feat order (written once per row by the
-  // rollout's actor): replaces the per-member f64 obs / act loads and scaler transform
+  // rollout's actor; wide models: [B][64], written by rollout_xs_wide_kernel): replaces the per-member
+  // f64 obs / act loads and scaler transform
   const float* xs;
   int ntiles;             // tiles per member in the grid
   int xcd_members;        // H = 400 f16x3 kernel: 1 = every XCD owns E / 8 members (set by launch_f16s)

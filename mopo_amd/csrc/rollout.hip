@@ -10,6 +10,7 @@
 //   rollout_compact   order-preserving non-terminal compaction  obs = next_obs[~term] (mopo.py:753-758)
 //   step_advance      steps_added / pool pointer & size (mopo.py:748; flexible_replay_pool.py:45-48)
 #include "actor.h"
+#include "mlp_tile.h"
 
 #include <vector>
 
@@ -34,7 +35,7 @@ struct Rollout {
   int wpk_hp = 0, wpk_f16 = 0;
   uint32_t* pen;
   int32_t* sel;
-  float* xs;        // [B][32] the ensemble's scaled input rows (written by the actor)
+  float* xs;        // [B][32] the ensemble's scaled input rows (written by the actor); wide models [B][64]
   float* mean_sel;
   float* std_sel;
   float* mean_all = nullptr;  // [E][Bmax][D], allocated on first use (mean-distance penalty / deterministic)
@@ -135,6 +136,33 @@ struct PostArgs {
   int64_t all_stride;
   int pen_dist, det;
 };
+
+// A wide model's scaled input rows (internal.h bnn_wide): xs[row][64] in slot_feat(., IN) order,
+// (concat(obs, act) - mu) / sigma as bnn_fwd_kernel computes it from the raw row.  The actor's own writer
+// (actor_finish) covers 32 slots; wide rollouts run this kernel behind the actor instead, so the actor
+// kernels stay as they are.  One thread per quad of slots, 16 threads per row: 256 B contiguous per row.
+__global__ __launch_bounds__(256) void rollout_xs_wide_kernel(const double* __restrict__ obs,
+                                                              const float* __restrict__ act, int O, int A,
+                                                              const float* __restrict__ mu,
+                                                              const float* __restrict__ sigma, int64_t B,
+                                                              const int* __restrict__ d_count, float* __restrict__ xs) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t row = i >> 4, count = d_count ? (int64_t)*d_count : B;
+  if (row >= B || row >= count) return;
+  const int q = (int)(i & 15);
+  f32x4 v;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int k = slot_feat(4 * q + t, O + A);
+    float x = 0.f;
+    if (k >= 0) {
+      const float raw = k < O ? (float)obs[row * O + k] : act[row * A + (k - O)];
+      x = (raw - mu[k]) / sigma[k];
+    }
+    v[t] = x;
+  }
+  *reinterpret_cast<f32x4*>(xs + row * XS_STRIDE_WIDE + 4 * q) = v;
+}
 
 // FakeEnv post-processing of one horizon step (fake_env.py:66-115) for POST_RPB rows per block, one
 // 32-lane group per row and one lane per output dim d < D = O + 1: every load and store of the row's
@@ -467,16 +495,23 @@ static int run_impl(Rollout* h, const mopo_rollout_args* a, const mopo_pool_desc
     aa.alone = !split;
     aa.act_uni = a->d_act_uniform ? a->d_act_uniform + ((int64_t)i * B + off) * A : nullptr;
     aa.elites = a->d_elites; aa.n_elites = a->n_elites;
-    aa.xs = h->xs + off * XS_STRIDE; aa.xs_mu = bnn->dev.mu; aa.xs_sigma = bnn->dev.sigma; aa.xs_in = bnn->dev.IN;
+    const bool wide = bnn->dev.KG0 > 2;   // internal.h bnn_wide: 64-slot xs rows, written behind the actor
+    float* xs = h->xs + off * xs_stride(bnn->dev.KG0);
+    aa.xs = wide ? nullptr : xs; aa.xs_mu = bnn->dev.mu; aa.xs_sigma = bnn->dev.sigma; aa.xs_in = bnn->dev.IN;
     {
       KTimer t(h, KC_ACTOR, ss);
       if (launch_actor(aa, ss)) return -1;
+      if (wide) {
+        hipLaunchKernelGGL(rollout_xs_wide_kernel, dim3(ceil_div((int)n, 16)), dim3(256), 0, ss, h->obs[oc] + off * O,
+                           h->act + off * A, O, A, bnn->dev.mu, bnn->dev.sigma, n, cnt, xs);
+        MOPO_HIP(hipGetLastError());
+      }
     }
     if (after_actor) MOPO_HIP(hipEventRecord(after_actor, ss));
 
     FwdArgs f{};
     f.in = FwdIn{h->obs[oc] + off * O, 1, O, h->act + off * A, 0, A};
-    f.B = n; f.d_count = cnt; f.xs = h->xs + off * XS_STRIDE;
+    f.B = n; f.d_count = cnt; f.xs = xs;
     f.pen_bits = h->pen + off; f.sel = det ? nullptr : h->sel + off; f.mean_sel = h->mean_sel + off * D;
     f.std_sel = h->std_sel + off * D;
     f.mean_all = need_all ? h->mean_all + off * D : nullptr;
@@ -586,7 +621,7 @@ extern "C" int mopo_rollout_create(mopo_rollout_t* out, mopo_bnn_t bnn, int64_t 
   const int nblk = ceil_div((int)B, PB);
   size_t sz[] = {(size_t)B * O * 8, (size_t)B * O * 8, (size_t)B * 8, (size_t)B * 8, (size_t)B * A * 4,
                  (size_t)B * 4,     (size_t)B * 4,     (size_t)B * D * 4, (size_t)B * D * 4, (size_t)B,
-                 (size_t)nblk * 4,  32,                (size_t)B * XS_STRIDE * 4};
+                 (size_t)nblk * 4,  32,                (size_t)B * xs_stride(b->dev.KG0) * 4};
   size_t off[13], tot = 0;
   for (int i = 0; i < 13; ++i) { off[i] = tot; tot += (sz[i] + 255) & ~(size_t)255; }
   if (hipMalloc(&h->mem, tot) != hipSuccess) { delete h; return fail("mopo_rollout_create: out of device memory"); }
