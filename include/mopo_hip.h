@@ -278,7 +278,13 @@ int mopo_rollout_profile_read(mopo_rollout_t h, double* ms, int64_t* launches, i
  * (target_init, mopo.py:449-450); log_alpha initial value (mopo.py:357-360); Adam lr / gamma / tau /
  * reward_scale / target_entropy as MOPO.__init__ (mopo.py:56-61, 171-174).  batch = 256 in the
  * reference (sampler batch_size), of which n_env rows come from the env pool (int(256*real_ratio),
- * mopo.py:801-816). */
+ * mopo.py:801-816).
+ * Limits (refused here otherwise, each with a message naming it): obs_dim <= 31 (the policy's layer-1 inputs and
+ * its bias column in one 32-wide group, as in the rollout actor), act_dim <= 8 (the head's 8-wide action
+ * records), hidden a multiple of 16 and <= 256, batch <= 1024.  The critics' inputs obs_dim + act_dim may
+ * therefore reach 39: handles with obs_dim + act_dim >= 32 run the wide layer-1 form of the forward blocks, the
+ * others exactly the kernels of one 32-wide group.  mopo_sac_param_count() and every buffer below follow
+ * obs_dim + act_dim as given. */
 typedef struct mopo_sac_s* mopo_sac_t;
 int mopo_sac_create(mopo_sac_t* out, int obs_dim, int act_dim, int hidden, int batch, int n_env,
                     const float* h_params, float log_alpha, float lr, float gamma, float tau,

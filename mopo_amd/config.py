@@ -59,7 +59,8 @@ TASKS = {
     'hopper_random': ('hopper', 'random-v0', 'hopper_random', 'd4rl/hopper-random-v0', int(1e6), 5, 1.0),
 }
 
-DIMS = {'halfcheetah': (17, 6), 'walker2d': (17, 6), 'hopper': (11, 3)}
+# ant / antangle: mopo/env/ant.py observes qpos[2:] (13) and qvel (14)
+DIMS = {'halfcheetah': (17, 6), 'walker2d': (17, 6), 'hopper': (11, 3), 'ant': (27, 8), 'antangle': (27, 8)}
 
 
 def deep_update(d, *updates):

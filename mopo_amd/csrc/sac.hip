@@ -78,6 +78,7 @@ struct Sac {
   unsigned* sync = nullptr;       // fused F2 + B1 launch: [nrb][2] row-block counters, then the timeout word
                                   //   (each on its own 128-B line: sac_rows.h SYNC_STRIDE)
   int fuse = 2;                   // 0: F1, F2, B1 separate; 1: F2 + B1 one launch; 2: F1 + F2 + B1 one launch
+  bool wide = false;              // obs_dim + act_dim >= 32: the forward blocks' wide layer-1 form (sac_rows.h WIDE_KS)
   float *dhead, *dh2p, *dh1p;
   // graph
   bool use_graph = true;
@@ -228,7 +229,8 @@ static int sac_step_impl(Sac* h, int par, const mopo_pool_desc* env, const mopo_
     if (h->fuse == 1) { f.sync_reset = h->sync; f.n_sync = SYNC_N * nrb; }   // this step's F2 -> B1 counters
     f.sync = h->sync;
     if (h->fuse < 2) {
-      hipLaunchKernelGGL(sac_fwd_kernel<false>, dim3(ncq, nrb, 4), dim3(256), 0, s, f);
+      if (h->wide) sac_launch_fwd_wide(false, f, s);
+      else hipLaunchKernelGGL(sac_fwd_kernel<false>, dim3(ncq, nrb, 4), dim3(256), 0, s, f);
       MOPO_HIP(hipGetLastError());
     }
   }
@@ -259,7 +261,8 @@ static int sac_step_impl(Sac* h, int par, const mopo_pool_desc* env, const mopo_
     f.st = Stamps{h->stamps, 1};
     f.sync = h->sync;
     if (h->fuse == 0) {
-      hipLaunchKernelGGL(sac_fwd_kernel<true>, dim3(ncq, nrb, 4), dim3(256), 0, s, f);
+      if (h->wide) sac_launch_fwd_wide(true, f, s);
+      else hipLaunchKernelGGL(sac_fwd_kernel<true>, dim3(ncq, nrb, 4), dim3(256), 0, s, f);
       MOPO_HIP(hipGetLastError());
     }
   }
@@ -298,9 +301,11 @@ static int sac_step_impl(Sac* h, int par, const mopo_pool_desc* env, const mopo_
     static_assert(B1_COLS == RB_COLS && B1_WAVES == 4, "the fused launches share the F1 / F2 grid");
     f2.st = Stamps{h->stamps, h->fuse >= 2 ? 0 : 1};
     if (h->fuse == 2) {
-      hipLaunchKernelGGL(sac_f12b1_kernel, dim3(ncq, nrb, 12), dim3(256), 0, s, f1, f2, d);
+      if (h->wide) sac_launch_f12b1_wide(f1, f2, d, s);
+      else hipLaunchKernelGGL(sac_f12b1_kernel, dim3(ncq, nrb, 12), dim3(256), 0, s, f1, f2, d);
     } else if (h->fuse == 1) {
-      hipLaunchKernelGGL(sac_f2b1_kernel, dim3(ncq, nrb, 8), dim3(256), 0, s, f2, d);
+      if (h->wide) sac_launch_f2b1_wide(f2, d, s);
+      else hipLaunchKernelGGL(sac_f2b1_kernel, dim3(ncq, nrb, 8), dim3(256), 0, s, f2, d);
     } else {
       hipLaunchKernelGGL(sac_dh1_kernel, dim3(ncq1, nrb, 4), dim3(B1_WAVES * 64), 0, s, d);
     }
@@ -365,9 +370,11 @@ extern "C" int mopo_sac_create(mopo_sac_t* out, int O, int A, int H, int batch, 
                                float log_alpha, float lr, float gamma, float tau, float reward_scale,
                                float target_entropy) {
   MOPO_REQUIRE(out && h_params, "mopo_sac_create: NULL argument");
-  MOPO_REQUIRE(O >= 1 && A >= 1 && A <= 8 && H >= 1, "mopo_sac_create: bad dims (act_dim <= 8)");
+  MOPO_REQUIRE(O >= 1 && A >= 1 && H >= 1, "mopo_sac_create: bad dims");
+  MOPO_REQUIRE(A <= 8, "mopo_sac_create: needs act_dim <= 8 (the policy head's 8-wide action records)");
   MOPO_REQUIRE(batch >= 1 && batch <= 1024, "mopo_sac_create: batch must be in [1, 1024]");
-  MOPO_REQUIRE(O + A <= 31, "mopo_sac_create: obs_dim + act_dim must be <= 31 (layer-1 inputs + the bias in one 32-wide group)");
+  MOPO_REQUIRE(O <= 31, "mopo_sac_create: needs obs_dim <= 31 (the policy's layer-1 inputs + the bias in one 32-wide group)");
+  static_assert(31 + 8 <= WIDE_MAX_W, "the wide layer-1 form covers every accepted obs_dim + act_dim");
   MOPO_REQUIRE(H % 16 == 0 && H <= 256, "mopo_sac_create: hidden width must be a multiple of 16, <= 256");
   MOPO_REQUIRE(n_env >= 0 && n_env <= batch, "mopo_sac_create: n_env must be in [0, batch]");
   Sac* h = new Sac();
@@ -400,6 +407,7 @@ extern "C" int mopo_sac_create(mopo_sac_t* out, int O, int A, int H, int batch, 
   f(&h->logp_s, 2 * ns); f(&h->logp_n, 2 * ns); f(&h->eps_s, ns * EPW); f(&h->eps_n, ns * EPW);
   reg.push_back({(void**)&h->sync, (size_t)(SYNC_N * (ns / 16) + SYNC_GLOBAL) * SYNC_STRIDE * 4});
   h->fuse = sac_fuse_default();
+  h->wide = O + A > 31;           // the critics' layer 1 (W inputs + the bias) no longer fits 8 k-steps
   for (int i = 0; i < 4; ++i) { f(&h->dq[i], n); f(&h->dh1[i], n * H); }
   f(&h->dhead, n * 2 * A); f(&h->dh2p, n * H); f(&h->dh1p, n * H);
   size_t total = 0;

@@ -5,7 +5,7 @@
 // sums in a fixed order (bit-reproducible, no atomics, no in-launch hand-off).
 //
 //   F1  sac_fwd_kernel<false>: pi(s), pi(s'), Q1(s,a), Q2(s,a): layer 1 (recomputed per block from the
-//       <= 31 inputs) + layer 2 + the partial dots of the block's 64 outputs with the output layer
+//       <= 39 inputs) + layer 2 + the partial dots of the block's 64 outputs with the output layer
 //       ([W_mean | W_log_std] for the policy, W3 for a critic)                   (mopo.py:298-324)
 //   F2  sac_fwd_kernel<true>: Q1/Q2(s, pi(s)) with the main critics, Qt1/Qt2(s', pi(s')) with the
 //       targets; the prologue sums pi's partials of its 16 rows into the squashed-Gaussian head
@@ -633,11 +633,13 @@ struct FwdLds {
 // One forward row-block workgroup: column block cq, row block rb, instance ii (grid indices, SGPRs: the
 // instance's fields then come from the kernel arguments by scalar loads -- a divided linear index made them
 // VGPRs, and every buffer descriptor built from them needed a waterfall loop).  H <= GKC, H % 16 == 0.
+// KS: the 4-deep MFMA k-steps layer 1 is unrolled to (k1 + 1 <= 4 KS: the inputs and the bias column); 8 for
+// obs_dim + act_dim <= 31, WIDE_KS for the wide critics (below).
 // FZ, the fusion level: 0 a launch of its own; 1 F2 inside sac_f2b1_kernel (F2 + B1); 2 F1 or F2 inside
 // sac_f12b1_kernel (F1 + F2 + B1).  A fused block's stores that a later phase of the launch reads are
 // write-through, and the block ends by signalling its row block's counter; a fused F2 block (FZ = 2) issues
 // its weight operands, then waits for its row block's pi blocks of F1 before loading the head's partials.
-template <bool HEAD, int FZ>
+template <bool HEAD, int FZ, int KS = 8>
 static __device__ __forceinline__ void fwd_block(const FwdArgsR a, int cq, int rb, int ii, FwdLds& L) {
   constexpr bool SC = HEAD ? FZ >= 1 : FZ >= 2;   // this block's stores are handed over in-launch
   float* As = L.As;
@@ -664,13 +666,13 @@ static __device__ __forceinline__ void fwd_block(const FwdArgsR a, int cq, int r
   const int r = lane & 15, q4 = lane >> 4;
   const int row = i0 + r;
   const int k1 = p.k1, ns = (k1 + 4) >> 2, sb = k1 >> 2;
-  float xb[8], wa[4][8], bv[4];
+  float xb[KS], wa[4][KS], bv[4];
   {
     const auto dx = rsrc(p.x, (int64_t)(n - 1) * p.ldx + p.kx);
     const auto dw = rsrc(p.w1, (int64_t)k1 * H);
     const auto db = rsrc(p.b1, H);
 #pragma unroll
-    for (int s = 0; s < 8; ++s) {
+    for (int s = 0; s < KS; ++s) {
       const int j = 4 * s + q4;
       const float v = bload(dx, (j < p.kx && row < n) ? row * p.ldx + j : -1);
       xb[s] = j == k1 ? 1.f : v;
@@ -682,11 +684,11 @@ static __device__ __forceinline__ void fwd_block(const FwdArgsR a, int cq, int r
       // W1 rows j >= k1 fall past the descriptor's range (k1 H) and read 0; a lane past H reads nothing
       const int vb = k < H ? (q4 * H + k) * 4 : (1 << 30);
 #pragma unroll
-      for (int s = 0; s < 8; ++s)
+      for (int s = 0; s < KS; ++s)
         wa[kt][s] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(dw, vb + 16 * s * H, 0, 0));
 #else
 #pragma unroll
-      for (int s = 0; s < 8; ++s) {
+      for (int s = 0; s < KS; ++s) {
         const int j = 4 * s + q4;
         wa[kt][s] = bload(dw, (j < k1 && k < H) ? j * H + k : -1);
       }
@@ -755,7 +757,7 @@ static __device__ __forceinline__ void fwd_block(const FwdArgsR a, int cq, int r
     }
     lds_barrier();
 #pragma unroll
-    for (int s = 0; s < 8; ++s) {
+    for (int s = 0; s < KS; ++s) {
       const int j = 4 * s + q4;
       if (j >= p.kx && j < k1) xb[s] = act_s[r][(j - p.kx) & 7];
     }
@@ -765,12 +767,12 @@ static __device__ __forceinline__ void fwd_block(const FwdArgsR a, int cq, int r
 #pragma unroll
   for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
-    for (int s = 0; s < 8; ++s)
+    for (int s = 0; s < KS; ++s)
       if (s == sb && q4 == (k1 & 3)) wa[kt][s] = bv[kt];
   {
     f32x4 acc[4] = {zero4(), zero4(), zero4(), zero4()};
 #pragma unroll
-    for (int s = 0; s < 8; ++s)
+    for (int s = 0; s < KS; ++s)
       if (s < ns)
 #pragma unroll
         for (int kt = 0; kt < 4; ++kt) acc[kt] = mfma4(wa[kt][s], xb[s], acc[kt]);
@@ -1108,11 +1110,16 @@ static __device__ __forceinline__ void dh1_block(const Dh1Args a, int x, int y, 
   stamp(a.st, 4);
 }
 
+#ifndef MOPO_SAC_NARROW_KERNELS
+#define MOPO_SAC_NARROW_KERNELS 1   // sac_wide.hip sets 0: the non-template kernels below are sac.hip's alone
+#endif
+#if MOPO_SAC_NARROW_KERNELS
 // B1 as its own launch: grid (ncq1, nrb, 4), B1_WAVES-wave workgroups
 static __global__ __launch_bounds__(B1_WAVES * 64, 1) void sac_dh1_kernel(const Dh1Args a) {
   __shared__ __attribute__((aligned(16))) Dh1Lds S;
   dh1_block<0>(a, blockIdx.x, blockIdx.y, blockIdx.z, S);
 }
+#endif
 
 // F2 and B1 as ONE launch, grid (ncq, nrb, 8): z < 4 the F2 blocks (instance z), z >= 4 the B1 blocks (B1's
 // z - 4).  Blocks are dispatched in linear-id order (z-major), so every F2 block is resident or done before a
@@ -1123,6 +1130,7 @@ union F2B1Lds {
   FwdLds f;
   Dh1Lds b;
 };
+#if MOPO_SAC_NARROW_KERNELS
 static __global__ __launch_bounds__(256, 2) void sac_f2b1_kernel(const FwdArgsR f, const Dh1Args b) {
   __shared__ __attribute__((aligned(16))) F2B1Lds S;
   if (blockIdx.z < 4)
@@ -1145,5 +1153,23 @@ static __global__ __launch_bounds__(256, 2) void sac_f12b1_kernel(const FwdArgsR
   else
     dh1_block<2>(b, blockIdx.x, blockIdx.y, blockIdx.z - 8, S.b);
 }
+#endif
+
+// ---- the wide forms: critic inputs W = obs_dim + act_dim in [32, 39] (obs_dim <= 31, act_dim <= 8), whose layer 1
+// (W inputs + the bias column) takes 9 or 10 4-deep k-steps instead of the 8 of one 32-wide group.  The same
+// blocks with KS = WIDE_KS layer-1 k-steps: 8 more W1 operand registers and 2 more input registers per lane
+// (wa[4][10], xb[10]), nothing else changes -- k-steps past (k1 + 4) >> 2 are skipped, their operands read 0 past
+// the descriptors' ranges.  The policy instances of F1 (k1 = obs_dim <= 31) run the same KS = WIDE_KS blocks (one
+// code path per launch; they skip steps 8 and 9).  Only handles with W >= 32 launch these (mopo_sac_create), so
+// the narrow instantiations above keep their registers and occupancy.  Grids, LDS, hand-offs and the dispatch-
+// order argument of the fused forms are the narrow kernels'.
+constexpr int WIDE_KS = 10;          // (39 + 4) >> 2
+constexpr int WIDE_MAX_W = 4 * WIDE_KS - 1;
+// The wide kernels are compiled in sac_wide.hip, a translation unit of their own (the narrow kernels' code
+// generation in sac.hip then does not depend on them); sac.hip launches them through these.  Grids as the
+// narrow launches: F1 / F2 (ncq, nrb, 4), F2 + B1 (ncq, nrb, 8), F1 + F2 + B1 (ncq, nrb, 12), 256 threads.
+void sac_launch_fwd_wide(bool head, const FwdArgsR& f, hipStream_t s);
+void sac_launch_f2b1_wide(const FwdArgsR& f2, const Dh1Args& b, hipStream_t s);
+void sac_launch_f12b1_wide(const FwdArgsR& f1, const FwdArgsR& f2, const Dh1Args& b, hipStream_t s);
 
 }  // namespace mopo

@@ -40,6 +40,9 @@ class SAC:
       save_full_state=False, **kwargs)`` -- softlearning/algorithms/sac.py:26-47: the dims come from the
       environment's spaces, the hidden width from the policy / Qs (``hidden_layer_sizes`` or
       ``hidden_sizes``, default 256 x 2); ``pool`` becomes the default env pool of ``_do_training``.
+
+    Limits (refused at construction by ``mopo_sac_create``): ``obs_dim <= 31`` and ``act_dim <= 8``, so the
+    critics read up to 39 inputs (ant: 27 + 8); hidden widths up to 256; ``batch_size <= 1024``.
     """
 
     def __init__(self, obs_dim, act_dim=None, *args, **kwargs):
