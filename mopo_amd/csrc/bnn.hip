@@ -55,9 +55,10 @@ __global__ void pack_frags_kernel(const float* __restrict__ src, float* __restri
 // bf16 fragments for v_mfma_f32_16x16x32_bf16 (k-group of 32, permuted k order: mlp_tile.h):
 // frag (kg, nb), lane l (n = l&15, g = l>>4), element j = W[e][32 kg + bf16_kperm(g, j)][16 nb + n]
 // P > 1: fragment (kg, p, nb) holds part p of the split (split_bf16), laid out [e][kg][p][nb].
+// mstride: fragments per member in dst (KG P NB; more when the packed remainder follows, pack_frags_kpack_kernel)
 template <int P>
 __global__ void pack_frags_bf16_kernel(const float* __restrict__ src, short* __restrict__ dst, int E, int K, int N,
-                                       int KG, int NB, int perm_k, int perm_n) {
+                                       int KG, int NB, int perm_k, int perm_n, int64_t mstride) {
   int64_t total = (int64_t)E * KG * P * NB * 512;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
        i += (int64_t)gridDim.x * blockDim.x) {
@@ -77,7 +78,33 @@ __global__ void pack_frags_bf16_kernel(const float* __restrict__ src, short* __r
 #pragma unroll
     for (int q = 1; q < P; ++q)
       if (q == p) v = parts[q];
-    dst[i] = v;
+    dst[(e * mstride + (int64_t)(kg * P + p) * NB + nb) * 512 + (i & 511)] = v;
+  }
+}
+
+// The packed remainder k-group (mlp_tile.h kpack_slot) of a K-wide input whose last 32-deep k-group KG - 1 holds 2
+// real values per lane: one fragment per output block behind member e's (KG - 1) 3 NB full-depth fragments.
+// Element j of lane (g, n) = weight part kpack_slot(j).wp of W[e][slot_feat(32 (KG - 1) + 4 g + kpack_slot(j).k)][n].
+__global__ void pack_frags_kpack_kernel(const float* __restrict__ src, short* __restrict__ dst, int E, int K, int N,
+                                        int KG, int NB, int perm_n, int64_t mstride) {
+  int64_t total = (int64_t)E * NB * 512;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    int j = i & 7, lane = (i >> 3) & 63;
+    int64_t f = i >> 9;
+    int nb = f % NB;
+    int e = f / NB;
+    const KPackSlot sl = kpack_slot(j);
+    int k = slot_feat((KG - 1) * 32 + bf16_kperm(lane >> 4, sl.k), K), n = nb * 16 + (lane & 15);
+    if (perm_n == 1) n = slot_feat(n, N);
+    else if (perm_n == 2) n = head_col(n, N / 2);
+    short parts[3];
+    split_bf16<3>((k >= 0 && n >= 0 && k < K && n < N) ? src[((int64_t)e * K + k) * N + n] : 0.f, parts);
+    short v = parts[0];
+#pragma unroll
+    for (int q = 1; q < 3; ++q)
+      if (q == sl.wp) v = parts[q];
+    dst[(e * mstride + (int64_t)(KG - 1) * 3 * NB + nb) * 512 + (i & 511)] = v;
   }
 }
 
@@ -868,7 +895,8 @@ __global__ __launch_bounds__(WAVES * 64, R == 1 ? 2 : 1) void bnn_fwd_f16r_kerne
 // ---- ensemble forward over an LDS ring (bnn_fwd_ring_kernel): P = 2 is bnn_fwd_f16s_kernel's f16x3
 // arithmetic (BNN_F16_RING), P = 1 bnn_fwd_bf16_kernel's single-bf16 arithmetic (BNN_BF16_RING), product
 // for product, with the weight slices of all five layers as ONE stream (layer 0: P slices, each hidden
-// layer and the head: P KG; a slice is one weight part of one 32-deep k-group).  Slice j + DEPTH - 1 is
+// layer and the head: P KG -- fewer with the head's parts merged (HPS) and the packed remainder (KP) below; a
+// slice is one weight part of one 32-deep k-group).  Slice j + DEPTH - 1 is
 // copied while slice j is consumed, so DEPTH - 1 slices are in flight across every barrier: the barrier is
 // a raw s_barrier behind a counted `s_waitcnt vmcnt(N)` that retires only slice j's copies (N = the later
 // slices' copies per wave; __syncthreads() would drain vmcnt(0)), and no layer starts on an exposed copy
@@ -925,7 +953,11 @@ __global__ __launch_bounds__(WAVES * 64, R == 1 ? 2 : 1) void bnn_fwd_f16r_kerne
 #endif
 // KG0B: 32-deep k-groups of the input row (2: wide models, up to 64 inputs; layer 0 then owns P KG0B slices,
 // w0b is [E][KG0B][P][NB2] and the xs rows lie 32 KG0B floats apart)
-template <int NB2, int NBO, int MODE, int WAVES, int P, int DEPTH, int NBU = NB2, int KG0B = 1>
+// KP (internal.h bnn_kpack; bf16x6, H = 197..200): the last k-group of every hidden-width input, 2 real values per
+// lane, is ONE slice of one packed fragment per output block (mlp_tile.h kpack_slot) behind one barrier, run as
+// two MFMAs per block (the second half full) -- instead of P slices and P (P + 1) / 2 half-zero 16-deep MFMAs.
+// Every product is the same exact bf16 x bf16 one; only the f32 accumulation order of that k-group differs.
+template <int NB2, int NBO, int MODE, int WAVES, int P, int DEPTH, int NBU = NB2, int KG0B = 1, bool KP = false>
 __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_MINB) * 4 / WAVES > 0)
                                              ? (P == 3 ? BNN_RING_MINB_X6 : BNN_RING_MINB) * 4 / WAVES : 1) void bnn_fwd_ring_kernel(const BnnDev w,
                                                                                             const FwdArgs a) {
@@ -939,9 +971,14 @@ __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_
   // (its P NBO fragments are contiguous in the packing), so the narrow head runs behind KG barriers, not P KG
   constexpr int HPS = BNN_RING_HEAD_MERGE && Stage<P * NBO, WAVES>::SLOTS <= Stage<NB2, WAVES>::SLOTS ? P : 1;
   constexpr int P0 = P * KG0B;   // layer 0's slices
-  constexpr int KG = NB2 / 2, NS = P0 + 3 * KG * P + KG * (P / HPS);
-  constexpr int JHEAD = P0 + 3 * KG * P;  // the head's first slice
   constexpr bool KH = NBU < NB2;
+  static_assert(!KP || (P == 3 && KH), "the packed remainder is the 3-part split's, behind an odd block count");
+  // a hidden-width input's k-groups: KGF as full-depth slices (P per hidden layer, P / HPS in the head), then,
+  // KP, the packed remainder slice
+  constexpr int KG = NB2 / 2, KGF = KP ? KG - 1 : KG;
+  constexpr int SLH = KGF * P + KP, SLD = KGF * (P / HPS) + KP;   // slices of a hidden layer, of the head
+  constexpr int NS = P0 + 3 * SLH + SLD;
+  constexpr int JHEAD = P0 + 3 * SLH;  // the head's first slice
   constexpr int SLOT = Stage<(NB2 > HPS * NBO ? NB2 : HPS * NBO), WAVES>::SLOTS * 256;
   constexpr int BIAS_LDS = (NB2 * 4 + 63) / 64 * 256;
   // two bias slots: layer L's bias (slot L & 1) goes out at the top of layer L - 1's first slice, so it
@@ -965,23 +1002,25 @@ __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_
     mx = fmaxf(mx, __shfl_xor(mx, 16));
     return fmaxf(mx, __shfl_xor(mx, 32));
   };
-  // slice stream: layer L (0 input, 1..3 hidden, 4 head) owns slices [P0 + P KG (L - 1), ...) (layer 0: [0, P0))
+  // slice stream: layer L (0 input, 1..3 hidden, 4 head) owns slices [P0 + SLH (L - 1), ...) (layer 0: [0, P0))
   const float* src[5];
   src[0] = w.w0b + (int64_t)e * P0 * NB2 * 256;
 #pragma unroll
-  for (int l = 0; l < 3; ++l) src[1 + l] = w.whb + ((int64_t)l * E + e) * KG * P * NB2 * 256;
-  src[4] = w.whdb + (int64_t)e * KG * P * NBO * 256;
+  for (int l = 0; l < 3; ++l) src[1 + l] = w.whb + ((int64_t)l * E + e) * SLH * NB2 * 256;
+  src[4] = w.whdb + (int64_t)e * (KGF * P + KP) * NBO * 256;
   auto issue = [&](auto jc) {  // every wave's copies of slice J (PER per wave, pads re-read a fragment)
     constexpr int J = decltype(jc)::value;
     if constexpr (J < NS) {
-      constexpr int L = J < P0 ? 0 : 1 + (J - P0) / (P * KG);
-      constexpr int NF = L == 4 ? HPS * NBO : NB2;
-      constexpr int s = J - (L == 0 ? 0 : P0 + P * KG * (L - 1));
-      constexpr int NFU = L == 4 ? HPS * NBO : NBU;   // the slice's used fragments (its first NFU)
+      constexpr int L = J < P0 ? 0 : (J >= JHEAD ? 4 : 1 + (J - P0) / SLH);
+      constexpr int NF = L == 4 ? HPS * NBO : NB2;   // fragments per slice in memory (the slice stride)
+      constexpr int s = J - (L == 0 ? 0 : P0 + SLH * (L - 1));
+      // the slice's copied fragments: the head's packed remainder holds NBO, every other slice NF
+      constexpr int NFC = KP && J == NS - 1 ? NBO : NF;
+      constexpr int NFU = L == 4 ? NFC : NBU;   // the slice's used fragments (its first NFU)
       if constexpr (WAVES == 4 && NFU % 4 == 1)   // 13 of 14 (H = 200), the 9-fragment head: no pad copies
         stage_slice_quarters<NFU, WAVES, RBUF>(src[L] + s * NF * 256, lds + (J % DEPTH) * SLOT, wv, lane);
       else
-        stage_slice<NF, WAVES, RBUF>(src[L] + s * NF * 256, lds + (J % DEPTH) * SLOT, wv, lane);
+        stage_slice<NFC, WAVES, RBUF>(src[L] + s * NF * 256, lds + (J % DEPTH) * SLOT, wv, lane);
     }
   };
   const int64_t bs = w.BS;
@@ -1073,7 +1112,8 @@ __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_
     if constexpr (F16) row_scale(row_max(mx), s_in, inv_row);
   };
   auto act = [&](int c, int j) {  // y' (FOLD: y' s) of value j of k-group c (the padding block stays 0)
-    if (j < 4 || 2 * c + 1 < NBU) {
+    // KP: the packed remainder k-group consumes its values 0 and 1 only
+    if ((j < 4 || 2 * c + 1 < NBU) && !(KP && c == KG - 1 && j >= 2)) {
       const float u = hf[c][j];
       hf[c][j] = FOLD ? u * __builtin_amdgcn_rcpf(fmaf(__builtin_amdgcn_exp2f(u), inv_row, inv_row)) : swish_log2(u);
     }
@@ -1117,30 +1157,59 @@ __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_
       for (int j = 0; j < 8; ++j) cur[0][j] = to_bf16(v[j]);
     }
   };
-  // layer L: NBL output blocks (NBUL used), KGL k-groups of input `in`, slices [J0, J0 + P KGL)
+  // the packed remainder's operands (mlp_tile.h kpack_slot) from the k-group's values 0 and 1: cur[0] the first
+  // MFMA's four dwords, cur[1] the second one's two (upper half zero); whole-dword writes only
+  // (split_f16_pair_prescaled)
+  auto parts_rem = [&](const float (&v)[8]) {
+    if constexpr (P == 3) {
+      uint32_t pr[3];
+      split_bf16_pair<3>(v[0], v[1], pr);
+      u32x4v bf, bh;
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        bf[d] = pr[kpack_slot(2 * d).xp];
+        bh[d] = d < 2 ? pr[kpack_slot(d < 2 ? 8 + 2 * d : 8).xp] : 0u;
+      }
+      cur[0] = __builtin_bit_cast(bf16x8, bf);
+      cur[1] = __builtin_bit_cast(bf16x8, bh);
+    }
+  };
+  // layer L: NBL output blocks (NBUL used), KGL k-groups of input `in`, slices [J0, J0 + SLL)
   auto layer = [&](auto Lc, auto& in) {
     constexpr int L = decltype(Lc)::value;
     constexpr int KGL = L == 0 ? KG0B : KG, NBL = L == 4 ? NBO : NB2, NBUL = L == 4 ? NBO : NBU;
     constexpr bool KHL = L > 0 && KH;
     constexpr bool DEFER = DEF && L > 0;   // `in` holds u; y' made one k-group ahead
-    constexpr int J0 = L == 0 ? 0 : P0 + P * KG * (L - 1);
+    constexpr int J0 = L == 0 ? 0 : P0 + SLH * (L - 1);
     constexpr int PPS = L == 4 ? HPS : 1, SPK = P / PPS;   // weight parts per slice, slices per k-group
+    constexpr bool KPL = KP && L > 0;   // the layer's last k-group is the packed remainder slice
+    constexpr int SLL = SPK * (KPL ? KGL - 1 : KGL) + KPL;
+    static_assert(SLL == (L == 0 ? P0 : L == 4 ? SLD : SLH), "the layer's share of the slice stream");
 #pragma unroll
     for (int nb = 0; nb < NBL; ++nb) acc[nb] = zero4();
     if constexpr (DEFER) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) act(0, j);
     }
-    RingRun<J0, J0 + SPK * KGL>::run([&](auto jc) {
-      constexpr int J = decltype(jc)::value, s = J - J0, kg = s / SPK, p0 = (s % SPK) * PPS;
+    RingRun<J0, J0 + SLL>::run([&](auto jc) {
+      constexpr int J = decltype(jc)::value, s = J - J0;
+      constexpr bool REM = KPL && s == SLL - 1;   // the packed remainder slice: one fragment per block
+      constexpr int kg = REM ? KGL - 1 : s / SPK, p0 = REM ? 0 : (s % SPK) * PPS;
       // made when the k-group is first consumed (layers > 0 under FOLD hold y' s already)
-      if constexpr (p0 == 0)
+      if constexpr (REM)
+        parts_rem(in[kg]);
+      else if constexpr (p0 == 0)
         parts(in[kg], std::integral_constant<bool, FOLD && (L > 0)>{}, std::integral_constant<bool, KHL && kg + 1 == KGL>{});
       // slice J landed (every later slice still in flight may stay so) ... for every wave, and every wave
-      // is done with the buffer slice J + DEPTH - 1 goes into (slice J - 1's)
+      // is done with the buffer slice J + DEPTH - 1 goes into (slice J - 1's).  N: the copies per wave of the
+      // later slices in flight, each from its own fragment count (the head's packed remainder holds NBO)
       constexpr int N = [] {
         int n = 0;
-        for (int i = 1; i <= DEPTH - 2; ++i) n += (J + i >= NS ? 0 : (((J + i >= JHEAD) ? HPS * NBO : NB2) + WAVES - 1) / WAVES);
+        for (int i = 1; i <= DEPTH - 2; ++i) {
+          const int Jx = J + i;
+          const int nf = Jx < JHEAD ? NB2 : (KP && Jx == NS - 1 ? NBO : HPS * NBO);
+          n += Jx >= NS ? 0 : (nf + WAVES - 1) / WAVES;
+        }
         return n;
       }();
       wait_vm_lgkm0<N>();
@@ -1156,7 +1225,7 @@ __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_
       auto frag = [&](int i) { return *reinterpret_cast<const bf16x8*>(b + (((i / NBUL) * NBL + i % NBUL) * 64 + lane) * 4); };
       // fragments read BNN_RING_PF ahead of their MFMAs, each read pinned ahead of the MFMAs that follow it
       // (left to itself the scheduler sinks it to just before its use: an exposed LDS latency per pair)
-      constexpr int PF = P == 3 ? BNN_RING_PF_X6 : BNN_RING_PF, NFR = PPS * NBUL;
+      constexpr int PF = P == 3 ? BNN_RING_PF_X6 : BNN_RING_PF, NFR = REM ? NBUL : PPS * NBUL;
       bf16x8 fq[PF];
 #pragma unroll
       for (int k = 0; k < PF; ++k)
@@ -1169,10 +1238,19 @@ __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_
         if constexpr (BNN_RING_PIN) __builtin_amdgcn_sched_barrier(0x0406);   // VALU, SALU, transcendentals may cross
         // part p of W meets the activation parts q < P - p, the lowest first (the product order of
         // layer_lds_split_f32; bf16x6 with x0 first measured the same: 91.4-91.6 vs 91.2-91.6M/s)
+        if constexpr (REM) {
+          // x0 (w0 + w1 + w2) + x1 w0 on the fragment's four dwords, then x2 w0 + x1 w1 on its low two (cur[1]'s
+          // upper two dwords are zero).  The second MFMA is the 32-deep opcode as well: a 16-deep MFMA taking its
+          // accumulator from the 32-deep one issued right before it gets no wait states from hipcc and read a
+          // stale accumulator on gfx950 (errors of 1e-2, varying run to run); the same opcode chains safely
+          acc[nb] = mfma_16x16x32<F16>(fr, cur[0], acc[nb]);
+          acc[nb] = mfma_16x16x32<F16>(fr, cur[1], acc[nb]);
+        } else {
 #pragma unroll
-        for (int q = P - 1 - p; q >= 0; --q)
-          acc[nb] = (KHL && kg + 1 == KGL) ? mfma_16x16x16_lo<F16>(fr, cur[q], acc[nb])
-                                           : mfma_16x16x32<F16>(fr, cur[q], acc[nb]);
+          for (int q = P - 1 - p; q >= 0; --q)
+            acc[nb] = (KHL && kg + 1 == KGL) ? mfma_16x16x16_lo<F16>(fr, cur[q], acc[nb])
+                                             : mfma_16x16x32<F16>(fr, cur[q], acc[nb]);
+        }
         // the next k-group's activations, spread over this k-group's P slices: values V p .. V p + V - 1,
         // value v after fragment max((v + 1) NBUL / V - 1, 0) (V = ceil(8 / P) per slice)
         if constexpr (DEFER && kg + 1 < KGL) {
@@ -1217,7 +1295,7 @@ __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_
                            (MODE == FWD_ROLLOUT && a.sel && ok_e) ? a.sel[row_e] : -1);
 }
 
-template <int NB2, int NBO, int P, int DEPTH, int KG0B = 1>
+template <int NB2, int NBO, int P, int DEPTH, int KG0B = 1, bool KP = false>
 static int launch_ring(const Bnn* h, int mode, FwdArgs a, hipStream_t s) {
   constexpr int WV = BNN_RING_WAVES;
   a.ntiles = (int)ceil_div((int)a.B, 16);
@@ -1227,9 +1305,9 @@ static int launch_ring(const Bnn* h, int mode, FwdArgs a, hipStream_t s) {
   // whole-block NB2 = 14 form (H = 209..224, no config) is not instantiated (it spilled 8-12 B)
   constexpr int NBU = NB2 == 14 ? NB2 - 1 : NB2;
   if (mode == FWD_PREDICT) {
-    hipLaunchKernelGGL((bnn_fwd_ring_kernel<NB2, NBO, FWD_PREDICT, WV, P, DEPTH, NBU, KG0B>), grid, block, 0, s, h->dev, a);
+    hipLaunchKernelGGL((bnn_fwd_ring_kernel<NB2, NBO, FWD_PREDICT, WV, P, DEPTH, NBU, KG0B, KP>), grid, block, 0, s, h->dev, a);
   } else {
-    hipLaunchKernelGGL((bnn_fwd_ring_kernel<NB2, NBO, FWD_ROLLOUT, WV, P, DEPTH, NBU, KG0B>), grid, block, 0, s, h->dev, a);
+    hipLaunchKernelGGL((bnn_fwd_ring_kernel<NB2, NBO, FWD_ROLLOUT, WV, P, DEPTH, NBU, KG0B, KP>), grid, block, 0, s, h->dev, a);
   }
   MOPO_HIP(hipGetLastError());
   return 0;
@@ -1237,6 +1315,16 @@ static int launch_ring(const Bnn* h, int mode, FwdArgs a, hipStream_t s) {
 // the ring kernel's shapes: H = 200 (NB2 14, 13 used), or a whole even block count (NBH = NB2) other than 14
 template <int NB2>
 static bool ring_shape(const Bnn* h) { return NB2 <= 16 && (NB2 == 14 ? h->dev.NBH == 13 : h->dev.NBH == NB2); }
+// the packed remainder's weight layout (set_params packs by the same predicate): the ring kernel's KP form only
+static bool kpack_shape(const Bnn* h) { return bnn_kpack(h->dtype, h->dev.NB2, h->dev.NBH, h->H); }
+// bf16x6 on the ring: the packed-remainder form where the weights are packed for it (H = 197..200)
+template <int NB2, int NBO, int KG0B = 1>
+static int launch_ring_x6(const Bnn* h, int mode, const FwdArgs& a, hipStream_t s) {
+  if constexpr (NB2 == 14)
+    if (kpack_shape(h)) return launch_ring<NB2, NBO, 3, BNN_RING_DEPTH_BF16, KG0B, true>(h, mode, a, s);
+  if (kpack_shape(h)) return fail("bnn bf16x6: packed-remainder weights at a shape without the packed kernel");
+  return launch_ring<NB2, NBO, 3, BNN_RING_DEPTH_BF16, KG0B>(h, mode, a, s);
+}
 
 #ifndef BNN_R13
 #define BNN_R13 1  // row blocks per wave at H = 200
@@ -1295,7 +1383,9 @@ static int launch_bf16_p(const Bnn* h, int mode, FwdArgs a, hipStream_t s) {
   if constexpr (P == 1 && BNN_BF16_RING && NB2 <= 16)
     if (ring_shape<NB2>(h)) return launch_ring<NB2, NBO, 1, BNN_RING_DEPTH_BF16>(h, mode, a, s);
   if constexpr (P == 3 && BNN_BF16X6_RING && NB2 <= 16)
-    if (ring_shape<NB2>(h)) return launch_ring<NB2, NBO, 3, BNN_RING_DEPTH_BF16>(h, mode, a, s);
+    if (ring_shape<NB2>(h)) return launch_ring_x6<NB2, NBO>(h, mode, a, s);
+  // bnn_fwd_bf16_kernel reads the unpacked [kg][p][nb] layout only
+  if (kpack_shape(h)) return fail("bnn bf16x6: a packed-remainder shape (H = 197..200) runs on the ring kernel only");
   constexpr int WV = P == 1 ? FWD_WAVES : BNN_SPLIT_WAVES;
   constexpr int PS = P == 1 ? 1 : (BNN_SPLIT_PS == 0 ? P : BNN_SPLIT_PS);
   a.ntiles = (int)ceil_div((int)a.B, 16);
@@ -1416,7 +1506,7 @@ template <int NB2>
 static int launch_wide16(const Bnn* h, int mode, const FwdArgs& a, hipStream_t s) {
   if (!ring_shape<NB2>(h)) return fail(kWide16Msg);
   if (h->dtype == DT_F16X3) return launch_ring<NB2, 4, 2, BNN_RING_DEPTH_F16, 2>(h, mode, a, s);
-  if (h->dtype == DT_BF16X6) return launch_ring<NB2, 4, 3, BNN_RING_DEPTH_BF16, 2>(h, mode, a, s);
+  if (h->dtype == DT_BF16X6) return launch_ring_x6<NB2, 4, 2>(h, mode, a, s);
   return fail(kWide16Msg);
 }
 
@@ -1610,7 +1700,10 @@ extern "C" int mopo_bnn_set_params(mopo_bnn_t hh, const float* const* arrs, int 
     // bf16 fragments: [E][KG0B][P][NB2] | [3][E][KG][P][NB2] | [E][KG][P][NBO], 256 floats (= 512 bf16) each;
     // KG0B = the input's 32-deep k-groups: 1, wide models (KG0 = 4) 2
     const int NB2 = d.NB2, KG = NB2 / 2, P = bf16_parts(h->dtype), KG0B = (KG0 + 1) / 2;
-    const int64_t f0 = (int64_t)E * KG0B * P * NB2, fh = 3LL * E * KG * P * NB2, fd = (int64_t)E * KG * P * NBO;
+    // bnn_kpack: the hidden-width inputs' last k-group is ONE packed slice behind the KG - 1 full ones' P
+    const bool kpack = bnn_kpack(h->dtype, NB2, NBH, H);
+    const int64_t SLM = kpack ? (KG - 1) * P + 1 : KG * P;   // slices per member of a hidden-width input
+    const int64_t f0 = (int64_t)E * KG0B * P * NB2, fh = 3LL * E * SLM * NB2, fd = (int64_t)E * SLM * NBO;
     if (!h->bbuf) MOPO_HIP(hipMalloc(&h->bbuf, (f0 + fh + fd) * 256 * sizeof(float)));
     h->bbuf_bytes = (f0 + fh + fd) * 256 * (int64_t)sizeof(float);
     float* b0f = reinterpret_cast<float*>(h->bbuf);
@@ -1633,8 +1726,18 @@ extern "C" int mopo_bnn_set_params(mopo_bnn_t hh, const float* const* arrs, int 
       }
     };
     int layer_idx = 0;
-    auto packh = [&](const float* src, size_t nsrc, float* dst, int K, int N, int KGb, int NB, int perm_n) -> int {
+    // KGb: the input's 32-deep k-groups; pk: its last one goes out packed (pack_frags_kpack_kernel)
+    auto packh = [&](const float* src, size_t nsrc, float* dst, int K, int N, int KGb, int NB, int perm_n,
+                     bool pk = false) -> int {
       MOPO_HIP(hipMemcpy(stage, src, nsrc * sizeof(float), hipMemcpyHostToDevice));
+      const int64_t mstride = (pk ? SLM : (int64_t)KGb * P) * NB;   // fragments per member
+      if (pk) {
+        const int64_t totr = (int64_t)E * NB * 512;
+        hipLaunchKernelGGL(pack_frags_kpack_kernel, dim3((int)std::min<int64_t>((totr + 255) / 256, 4096)), dim3(256), 0,
+                           0, stage, (short*)dst, E, K, N, KGb, NB, perm_n, mstride);
+        MOPO_HIP(hipGetLastError());
+        --KGb;   // the full-depth k-groups
+      }
       int64_t tot = (int64_t)E * KGb * P * NB * 512;
       int blocks = (int)std::min<int64_t>((tot + 255) / 256, 4096);
       if (h->dtype == DT_F16X3) {
@@ -1644,13 +1747,13 @@ extern "C" int mopo_bnn_set_params(mopo_bnn_t hh, const float* const* arrs, int 
                            1, perm_n, (const float*)scale_d);
       } else if (P == 3)
         hipLaunchKernelGGL(pack_frags_bf16_kernel<3>, dim3(blocks), dim3(256), 0, 0, stage, (short*)dst, E, K, N, KGb,
-                           NB, 1, perm_n);
+                           NB, 1, perm_n, mstride);
       else if (P == 2)
         hipLaunchKernelGGL(pack_frags_bf16_kernel<2>, dim3(blocks), dim3(256), 0, 0, stage, (short*)dst, E, K, N, KGb,
-                           NB, 1, perm_n);
+                           NB, 1, perm_n, mstride);
       else
         hipLaunchKernelGGL(pack_frags_bf16_kernel<1>, dim3(blocks), dim3(256), 0, 0, stage, (short*)dst, E, K, N, KGb,
-                           NB, 1, perm_n);
+                           NB, 1, perm_n, mstride);
       MOPO_HIP(hipGetLastError());
       MOPO_HIP(hipDeviceSynchronize());
       ++layer_idx;
@@ -1658,8 +1761,8 @@ extern "C" int mopo_bnn_set_params(mopo_bnn_t hh, const float* const* arrs, int 
     };
     if (rc == 0) rc = packh(W[0], (size_t)E * IN * H, b0f, IN, H, KG0B, NB2, 1);
     for (int l = 0; l < 3 && rc == 0; ++l)
-      rc = packh(W[1 + l], (size_t)E * H * H, bhf + (int64_t)l * E * KG * P * NB2 * 256, H, H, KG, NB2, 1);
-    if (rc == 0) rc = packh(head.data(), head.size(), bdf, H, 2 * D, KG, NBO, 2);
+      rc = packh(W[1 + l], (size_t)E * H * H, bhf + (int64_t)l * E * SLM * NB2 * 256, H, H, KG, NB2, 1, kpack);
+    if (rc == 0) rc = packh(head.data(), head.size(), bdf, H, 2 * D, KG, NBO, 2, kpack);
     if (rc == 0 && h->dtype == DT_F16X3)
       rc = hipMemcpy(wsc, inv_h.data(), 5 * E * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? 0
                                                                                                  : fail("bnn: scale copy");

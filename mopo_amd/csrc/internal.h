@@ -34,14 +34,24 @@ struct BnnDev {
   // addressed in float units like the f32 fragments; hidden width padded to NB2 = even(NBH)
   int NB2;
   const float* w0b;   // [E][KG0B][P][NB2], KG0B = (KG0 + 1) / 2 input k-groups of 32 (1; wide models 2)
-  const float* whb;   // [3][E][NB2/2][NB2]
-  const float* whdb;  // [E][NB2/2][NBO]
+  const float* whb;   // [3][E][NB2/2][P][NB2]  (bnn_kpack: [3][E][(NB2/2 - 1) P + 1][NB2], the last the packed remainder)
+  const float* whdb;  // [E][NB2/2][P][NBO]       (bnn_kpack: [E][(NB2/2 - 1) P + 1][NBO])
   const float* wscale;  // f16x3: [5][E] inverse power-of-two weight scales (layer 0, hidden 1..3, head)
 };
 
 enum { DT_FP32 = 0, DT_BF16 = 1, DT_BF16X3 = 2, DT_BF16X6 = 3, DT_F16X3 = 4 };
 // 16-bit parts per operand of a dtype (1 bf16, 2 bf16x3, 3 bf16x6, 2 f16x3; mlp_tile.h split_*)
 __host__ __device__ constexpr int bf16_parts(int dtype) { return dtype < 1 ? 1 : (dtype == DT_F16X3 ? 2 : dtype); }
+
+// k-steps a consumer must run in the last 16-deep k-group of a width-F input (4: no skip; mlp_tile.h slot_feat)
+__host__ __device__ constexpr int tail_steps(int F) { return (F & 15) == 0 ? 4 : ((F & 15) + 3) >> 2; }
+
+// Packed remainder k-group (mlp_tile.h kpack_slot): bf16x6 at H = 197..200, where the last 32-deep k-group of a
+// hidden-width input holds 2 real values per lane.  The packer (mopo_bnn_set_params) and every launch
+// decide from this one predicate; whb / whdb then hold (KG - 1) P + 1 slices per member instead of KG P.
+__host__ __device__ constexpr bool bnn_kpack(int dtype, int NB2, int NBH, int H) {
+  return dtype == DT_BF16X6 && NB2 == 14 && NBH == 13 && tail_steps(H) == 2;
+}
 
 struct Bnn {
   int E, O, A, H, smv, dtype;

@@ -33,8 +33,7 @@ __host__ __device__ __forceinline__ int head_col(int slot, int D) {
   return -1;
 }
 
-// k-steps a consumer must run in the last 16-deep k-group of a width-F input (4: no skip)
-__host__ __device__ constexpr int tail_steps(int F) { return (F & 15) == 0 ? 4 : ((F & 15) + 3) >> 2; }
+// (tail_steps(F), the k-steps a consumer must run in the last 16-deep k-group of a width-F input: internal.h)
 
 // ---- LDS-staged weight streaming ------------------------------------------------------------
 // A workgroup of WAVES waves shares one member; every k-group slice of a layer (NB fragments,
@@ -347,6 +346,39 @@ __device__ __forceinline__ void split_bf16_pair(float a, float b, uint32_t (&out
     }
   }
 }
+
+// ---- packed remainder k-group of the 3-part split (internal.h bnn_kpack; bnn.hip bnn_fwd_ring_kernel<KP>) ------
+// A width-F input with tail_steps(F) == 2 (H = 197..200) leaves every lane 2 real values k = 0, 1 in its last
+// 32-deep k-group (slot_feat: registers t = 0, 1 of the last block; elements 2..7 of the operand are padding).
+// The unpacked form runs that k-group as 3 weight slices and 6 half-zero 16-deep MFMAs per output block.  Packed,
+// the 6 products (x part p, w part q), p + q < 3, of the lane's 2 values are 12 element slots: one full
+// MFMA (slots 0..7) plus the low half of a second one (slots 8..11) against ONE weight fragment per output block,
+// whose four dwords {w0, w1, w2, w0} each hold a part's bf16 pair (k = 0 low, k = 1 high); the second MFMA meets
+// the fragment's dwords 0, 1 again (its activation operand's upper half is zero; it is issued as the 32-deep
+// opcode too, see bnn_fwd_ring_kernel).  Slot i sits in dword (i / 2) & 3 of its MFMA's operands, half i & 1.
+struct KPackSlot {
+  int k, xp, wp;   // the lane's real value (0, 1), activation part, weight part
+};
+constexpr int KPACK_SLOTS = 12;
+__host__ __device__ constexpr KPackSlot kpack_slot(int i) {
+  // per operand dword: 0..3 the 32-deep MFMA's, 4..5 the 16-deep one's
+  constexpr int XP[6] = {0, 0, 0, 1, 2, 1}, WP[6] = {0, 1, 2, 0, 0, 1};
+  return {i & 1, XP[i >> 1], WP[i >> 1]};
+}
+constexpr bool kpack_table_ok() {
+  for (int k = 0; k < 2; ++k)
+    for (int p = 0; p < 3; ++p)
+      for (int q = 0; q < 3; ++q) {
+        int n = 0;
+        for (int i = 0; i < KPACK_SLOTS; ++i) n += kpack_slot(i).k == k && kpack_slot(i).xp == p && kpack_slot(i).wp == q;
+        if (n != (p + q < 3 ? 1 : 0)) return false;
+      }
+  // the 16-deep MFMA's weight operand is the fragment's low two dwords
+  for (int i = 8; i < KPACK_SLOTS; ++i)
+    if (kpack_slot(i).wp != kpack_slot(i - 8).wp) return false;
+  return true;
+}
+static_assert(kpack_table_ok(), "every product (p, q), p + q < 3, exactly once per k, and no other");
 
 // PS: parts staged per slice (P: one slice of P * NB fragments per k-group; 1: P slices of NB).
 // F16: the parts are fp16 ("f16x3", split_f16_scaled) and the products run on the f16 MFMA.
