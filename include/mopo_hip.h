@@ -273,6 +273,37 @@ int mopo_rollout_run_staged_steps(mopo_rollout_t h, const mopo_rollout_args* a, 
 int mopo_rollout_profile(mopo_rollout_t h, int enable);
 int mopo_rollout_profile_read(mopo_rollout_t h, double* ms, int64_t* launches, int n);
 
+/* ---- model-based policy evaluation -------------------------------------------------------
+ * B episodes of up to T steps of the policy inside the learned model, entirely on the device: what
+ * RLAlgorithm._evaluation_paths / _evaluate_rollouts (softlearning/algorithms/rl_algorithm.py:258-304)
+ * compute in a real environment, with FakeEnv.step (fake_env.py:37-131) as the environment.  The
+ * returns are returns UNDER THE MODEL: biased wherever the model is wrong, not a D4RL score.
+ * Per step: actor -> ensemble -> FakeEnv post -> compaction, as mopo_rollout_run, but nothing enters a
+ * pool; each live row's rewards are added to its episode (row id - uid_offset) instead. */
+typedef struct {
+  int policy_deterministic; /* 1: actions tanh(mu) (get_action_meta's deterministic branch, mopo.py:481-482);
+                               0: sampled, the policy noise of mopo_rollout_run (d_eps_act or Philox) */
+  /* outputs (device), any may be NULL */
+  double* d_return;         /* [B] sum of unpenalized rewards samples[:, 0] (fake_env.py:89) */
+  double* d_pen_return;     /* [B] sum of penalized rewards (fake_env.py:115) */
+  double* d_pen_sum;        /* [B] sum of the penalty (fake_env.py:98-110) */
+  int32_t* d_length;        /* [B] steps taken */
+  uint8_t* d_terminated;    /* [B] 1: the episode ended by the termination rule, 0: it ran T steps */
+  double* d_stats;          /* [16]: 0-3 mean / min / max / population std of the returns, 4-7 the same of the
+                               lengths, 8 mean penalized return, 9 mean penalty per step (sum of d_pen_sum /
+                               sum of d_length), 10 terminated fraction, 11 B, 12-15 zero */
+} mopo_eval_args;
+
+/* `a` as for mopo_rollout_run, its parity-mode streams indexed [step][B] by the current compacted row,
+ * with horizon = T, the episode length cap: 1 <= T <= 4095 whatever the handle's max_horizon (the Philox
+ * step key is epoch * 4096 + 1 + step); d_steps may be NULL, else int64[T] live rows per step.  With
+ * policy_deterministic = 0 the episodes are exactly the trajectories mopo_rollout_run visits for the same
+ * args (same Philox keys, same kernels per row).  Compaction runs whenever term_kind is not
+ * MOPO_TERM_NONE; every 32 steps (environment MOPO_EVAL_POLL, 0: never) the live count is read back (a
+ * stream synchronisation) and the loop stops once no episode is alive -- the results do not depend on it.  policy_deterministic with
+ * rollout_random is refused.  The statistics are reduced in a fixed order: bit-reproducible. */
+int mopo_rollout_evaluate(mopo_rollout_t h, const mopo_rollout_args* a, const mopo_eval_args* e, void* stream);
+
 /* ---- SAC update (MOPO._do_training + _update_target) ------------------------------------
  * h_params: initial flat parameters (mopo_sac_param_count floats, layout above); target = copy
  * (target_init, mopo.py:449-450); log_alpha initial value (mopo.py:357-360); Adam lr / gamma / tau /

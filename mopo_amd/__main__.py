@@ -12,7 +12,9 @@ are accepted and ignored: one process drives one GPU here (multi-GPU is torchrun
 Offline additions: ``--data`` (local qlearning_dataset .npz: d4rl downloads are unavailable) --
 or ``$D4RL_DATASET_DIR/<task>.npz`` named after the config's ``pool_load_path`` -- ``--model-dir``
 (``<model_name>.mat``, bnn.py:276-281), ``--epochs`` and ``--ensemble-dtype`` / ``--actor-dtype``
-(the forward arithmetic; default f16x3, held to the fp32 parity tolerances).  ``--config`` is any
+(the forward arithmetic; default f16x3, held to the fp32 parity tolerances) and ``--model-eval-episodes`` /
+``--model-eval-length`` (episodes of the policy inside the learned model after every epoch; off by default).
+``--config`` is any
 importable module holding a ``params`` dict (examples/development/__init__.py:19-22), or one of the
 restated D4RL config names when the reference's ``examples`` package is not installed.
 """
@@ -40,6 +42,8 @@ def get_parser():
     p.add_argument('--epochs', type=int, default=None)
     p.add_argument('--ensemble-dtype', default=None, choices=DTYPES)
     p.add_argument('--actor-dtype', default=None, choices=('fp32', 'bf16x6', 'f16x3'))
+    p.add_argument('--model-eval-episodes', type=int, default=None)
+    p.add_argument('--model-eval-length', type=int, default=None)
     for f in ('--cpus', '--gpus', '--trial-cpus', '--trial-extra-cpus', '--max-failures'):
         p.add_argument(f, type=int, default=None)
     for f in ('--trial-gpus', '--trial-extra-gpus'):
@@ -68,7 +72,7 @@ def variant_spec(args):
     from .config import get_params
     params = get_params(args.config)
     kw = params['kwargs']
-    for k in ('ensemble_dtype', 'actor_dtype'):
+    for k in ('ensemble_dtype', 'actor_dtype', 'model_eval_episodes', 'model_eval_length'):
         if getattr(args, k) is not None:
             kw[k] = getattr(args, k)
     kw.setdefault('ensemble_dtype', default_ensemble_dtype(kw.get('hidden_dim', 200)))
@@ -101,9 +105,9 @@ def main(argv=None):
             rargv += ['--model-dir', args.model_dir]
         if args.epochs is not None:
             rargv += ['--epochs', str(args.epochs)]
-        for k in ('ensemble_dtype', 'actor_dtype'):
+        for k in ('ensemble_dtype', 'actor_dtype', 'model_eval_episodes', 'model_eval_length'):
             if getattr(args, k) is not None:
-                rargv += ['--' + k.replace('_', '-'), getattr(args, k)]
+                rargv += ['--' + k.replace('_', '-'), str(getattr(args, k))]
         run.main(rargv)
     return 0
 

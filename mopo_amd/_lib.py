@@ -39,6 +39,11 @@ class RolloutArgs(C.Structure):
                 ('rollout_random', c_int), ('d_act_uniform', c_void_p), ('actor_dtype', c_int)]
 
 
+class EvalArgs(C.Structure):
+    _fields_ = [('policy_deterministic', c_int), ('d_return', c_void_p), ('d_pen_return', c_void_p),
+                ('d_pen_sum', c_void_p), ('d_length', c_void_p), ('d_terminated', c_void_p), ('d_stats', c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/mopo_hip.h
 SIGNATURES = {
     'mopo_last_error': (C.c_char_p, []),
@@ -86,6 +91,7 @@ SIGNATURES = {
     'mopo_rollout_destroy': (c_int, [c_void_p]),
     'mopo_rollout_run': (c_int, [c_void_p, C.POINTER(RolloutArgs), C.POINTER(PoolDesc), c_void_p]),
     'mopo_rollout_run_staged': (c_int, [c_void_p, C.POINTER(RolloutArgs), C.POINTER(PoolDesc), c_void_p]),
+    'mopo_rollout_evaluate': (c_int, [c_void_p, C.POINTER(RolloutArgs), C.POINTER(EvalArgs), c_void_p]),
     'mopo_rollout_profile': (c_int, [c_void_p, c_int]),
     'mopo_rollout_profile_read': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     'mopo_sac_create': (c_int, [C.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_void_p, c_float,

@@ -9,47 +9,12 @@
 //                     (fake_env.py:72, 90-115; mopo.py:750-751)
 //   rollout_compact   order-preserving non-terminal compaction  obs = next_obs[~term] (mopo.py:753-758)
 //   step_advance      steps_added / pool pointer & size (mopo.py:748; flexible_replay_pool.py:45-48)
-#include "actor.h"
 #include "mlp_tile.h"
-
-#include <vector>
+#include "rollout.h"
 
 namespace mopo {
 
 enum { KC_START = 0, KC_ACTOR, KC_BNN, KC_POST, KC_COMPACT, KC_ADVANCE, KC_N };
-
-struct Rollout {
-  // optional live kernel timing: hipEvents recorded around every launch, per kernel class
-  bool profile = false;
-  std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> ev;
-  std::vector<hipEvent_t> pool_ev;
-  size_t ev_used = 0;
-  Bnn* bnn = nullptr;
-  int64_t Bmax = 0;
-  int Hmax = 0;
-  void* mem = nullptr;
-  double* obs[2];
-  int64_t* uid[2];
-  float* act;
-  float* wpk = nullptr;  // policy weights, fragment-major (pack_actor), repacked every run
-  int wpk_hp = 0, wpk_f16 = 0;
-  uint32_t* pen;
-  int32_t* sel;
-  float* xs;        // [B][32] the ensemble's scaled input rows (written by the actor); wide models [B][64]
-  float* mean_sel;
-  float* std_sel;
-  float* mean_all = nullptr;  // [E][Bmax][D], allocated on first use (mean-distance penalty / deterministic)
-  uint8_t* keep;
-  int* blockcnt;
-  int* cnt;  // [0] live rows this step, [1] survivors, [2 + k] rows of part k (split rollout)
-  static constexpr int MAXSPLIT = 4;
-  hipStream_t sp[MAXSPLIT] = {};        // streams of parts 1.. of the split rollout (run_impl)
-  hipEvent_t ev_fork[MAXSPLIT] = {}, ev_join[MAXSPLIT] = {};
-  // horizon state carried between step-range calls (mopo_rollout_run_staged_steps)
-  int oc = 0, uc = 0, next_step = 0;
-};
-
-constexpr int PB = 256;  // rows per block in post / compact
 
 // scoped hipEvent pair on the launch stream (only when profiling is enabled)
 struct KTimer {
@@ -76,7 +41,6 @@ struct KTimer {
 // Start states (mopo.py:740-741): a block's 64 rows draw their source rows first (one thread each), then the
 // block copies the 64 x O observations element-wise, so the f64 stores of consecutive threads are contiguous
 // (one thread per row, each storing its 136-B row, took 26 us per 100k rows)
-constexpr int START_ROWS = 64, START_TPB = 256;
 __global__ __launch_bounds__(START_TPB) void rollout_start_kernel(const float* env_obs, int64_t env_size,
                                                                   const int64_t* idx_in, int O, int64_t B,
                                                                   uint64_t seed, uint32_t step, int64_t uid_offset,
@@ -110,32 +74,6 @@ __global__ __launch_bounds__(START_TPB) void rollout_start_kernel(const float* e
     obs[(r0 + r) * O + k] = (double)env_obs[srcs[r] * O + k];
   }
 }
-
-struct PostArgs {
-  int O;
-  const int* cnt;
-  const double* obs;        // current obs f64 [B][O]
-  const int64_t* uid;
-  const float* mean_sel;    // [B][D]
-  const float* std_sel;
-  const uint32_t* pen;
-  const double* eps;        // injected [B][D] or NULL
-  uint64_t seed; uint32_t step;
-  float coeff;
-  int term_kind;
-  double* obs_next;         // [B][O]
-  uint8_t* keep;
-  int* blockcnt;
-  mopo_pool_desc pool;
-  int64_t stage_base;       // >= 0: staged layout
-  int64_t pool_off;         // pool layout: rows go to (state[0] + pool_off + row) % max_size
-  // every member's mean [E][all_stride][D] (the ensemble's mean_all), for the mean-distance penalty
-  // (pen_dist, fake_env.py:98-108) and deterministic steps (det, fake_env.py:69-70, 84-86)
-  const float* mean_all;
-  int E;
-  int64_t all_stride;
-  int pen_dist, det;
-};
 
 // A wide model's scaled input rows (internal.h bnn_wide): xs[row][64] in slot_feat(., IN) order,
 // (concat(obs, act) - mu) / sigma as bnn_fwd_kernel computes it from the raw row.  The actor's own writer
@@ -670,6 +608,7 @@ extern "C" int mopo_rollout_destroy(mopo_rollout_t hh) {
   if (h->mem) (void)hipFree(h->mem);
   if (h->wpk) (void)hipFree(h->wpk);
   if (h->mean_all) (void)hipFree(h->mean_all);
+  if (h->eval_mem) (void)hipFree(h->eval_mem);
   delete h;
   return 0;
 }

@@ -102,3 +102,30 @@ def perf_metrics(evaluation, min_ret, max_ret):
     if min_ret != max_ret:
         out['perf/NormalizedReturn'] = (out['perf/AverageReturn'] - min_ret) / (max_ret - min_ret)
     return out
+
+
+# ---- evaluation inside the learned model (ModelRollout.evaluate, csrc/rollout_eval.hip) -------------------
+# The episodes run in FakeEnv, not in the task: the returns are returns UNDER THE MODEL, biased wherever the
+# model is wrong (the policy is trained to exploit exactly those places as far as the penalty lets it).  They
+# are no D4RL score, so no perf/NormalizedReturn is derived from them.
+MODEL_EVAL_KEYS = ('return-average', 'return-min', 'return-max', 'return-std', 'episode-length-avg',
+                   'episode-length-min', 'episode-length-max', 'episode-length-std', 'penalized-return-average',
+                   'penalty-average', 'terminated-fraction')
+
+
+def model_evaluation_metrics(stats):
+    """The device statistics ``ModelRollout.evaluate(...)['stats']`` (f64[16]; the first eleven in
+    ``MODEL_EVAL_KEYS`` order) as evaluate_rollouts' OrderedDict plus ``penalized-return-average`` (mean
+    of the penalized returns, fake_env.py:115), ``penalty-average`` (mean penalty per step taken) and
+    ``terminated-fraction`` (episodes ended by the termination rule before the length cap)."""
+    s = stats.detach().cpu().numpy() if hasattr(stats, 'detach') else np.asarray(stats)
+    return OrderedDict((k, float(s[i])) for i, k in enumerate(MODEL_EVAL_KEYS))
+
+
+def model_evaluation_metrics_numpy(returns, lengths, penalized_returns, penalty_sums, terminated):
+    """The same dict from per-episode host arrays (what the device reduction must equal)."""
+    r, n = np.asarray(returns, np.float64), np.asarray(lengths, np.float64)
+    vals = (np.mean(r), np.min(r), np.max(r), np.std(r), np.mean(n), np.min(n), np.max(n), np.std(n),
+            np.mean(np.asarray(penalized_returns, np.float64)), np.sum(np.asarray(penalty_sums, np.float64)) / np.sum(n),
+            np.mean(np.asarray(terminated, np.float64)))
+    return OrderedDict((k, float(v)) for k, v in zip(MODEL_EVAL_KEYS, vals))

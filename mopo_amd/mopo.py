@@ -10,7 +10,9 @@ Differences that are deliberate: the rollout and the SAC steps run on the device
 batch (the reference runs them one ``session.run`` at a time, with the same batch rule per step);
 Evaluation rollouts (``_evaluation_paths`` / ``_evaluate_rollouts``, mopo.py:575-629) run when an
 ``evaluation_environment`` (gym API) is passed -- MuJoCo is not in this image, so the caller supplies
-it; without one the ``evaluation/*`` and ``perf/*`` keys are absent.  The dynamics model is trained once before the epoch loop
+it; without one the ``evaluation/*`` and ``perf/*`` keys are absent.  ``model_eval_episodes`` > 0 adds an
+offline estimate that needs no environment: episodes of the policy inside the learned model, on the device
+(``model_eval/*``; the return under the model, not a D4RL score).  The dynamics model is trained once before the epoch loop
 (mopo.py:526-531): one epoch when it was loaded from ``model_load_dir``, else to early stopping,
 on the device (``_train_model`` formats the env pool on the device in the holdout-permutation order).
 """
@@ -34,13 +36,16 @@ class MOPO:
                  model_name=None, model_load_dir=None, deterministic=False, network_kwargs=None, epoch_length=1000,
                  n_epochs=1000, n_train_repeat=1, batch_size=256, seed=88, reparameterize=True, max_model_t=None,
                  rollout_random=False, evaluation_environment=None, eval_n_episodes=10, eval_deterministic=True,
-                 max_path_length=1000, ensemble_dtype=None, actor_dtype=None, **kwargs):
+                 max_path_length=1000, ensemble_dtype=None, actor_dtype=None, model_eval_episodes=0,
+                 model_eval_length=None, **kwargs):
         """``ensemble_dtype``: the ensemble forward's arithmetic (``mopo_amd.bnn.DTYPES``), default
         ``DEFAULT_ENSEMBLE_DTYPE`` ('bf16x6': the f32 operands split exactly into 3 bf16 parts, 6 bf16
         MFMA products, f32 accumulate; 'fp32' above H = 256: ``bnn.default_ensemble_dtype``); 'fp32' runs
         exact-f32 MFMA, 'f16x3' ~22-bit operands.  ``actor_dtype``: the rollout policy forward ('fp32' /
         'bf16x6' / 'f16x3'; default the ensemble's for fp32 and bf16x6, else f16x3:
-        ``rollout.default_actor_dtype``)."""
+        ``rollout.default_actor_dtype``).  ``model_eval_episodes`` > 0: every epoch ends with that many
+        episodes of at most ``model_eval_length`` (default ``max_path_length``) steps of the policy inside the
+        learned model (``_evaluate_in_model``: ``model_eval/*`` diagnostics); 0, the default, runs none."""
         if kwargs.get('action_prior', 'uniform') != 'uniform':   # mopo.py:364 asserts the uniform prior
             raise AssertionError("MOPO's policy loss supports action_prior='uniform' only (mopo.py:364)")
         self._pool = pool                                   # device SimpleReplayPool of env data
@@ -87,6 +92,9 @@ class MOPO:
         from .evaluation import ref_scores
         self.min_ret, self.max_ret = ref_scores(model_name)                              # mopo.py:115-123
         self._model_train_metrics = None
+        self._model_eval_episodes = int(model_eval_episodes)
+        self._model_eval_length = int(max_path_length if model_eval_length is None else model_eval_length)
+        self._eval_rollout = None
 
     # -- mopo.py:675-687
     def _set_rollout_length(self):
@@ -198,6 +206,8 @@ class MOPO:
         t2 = time.perf_counter()
         evaluation = self._evaluate()
         t3 = time.perf_counter()
+        model_eval = self._evaluate_in_model()
+        t4 = time.perf_counter()
         diag = OrderedDict()
         diag.update(('evaluation/' + k, evaluation[k]) for k in sorted(evaluation))
         diag.update(('model/' + k, v) for k, v in metrics.items())
@@ -209,6 +219,9 @@ class MOPO:
         if evaluation:
             from .evaluation import perf_metrics
             diag.update(perf_metrics(evaluation, self.min_ret, self.max_ret))
+        if model_eval:
+            diag.update(('model_eval/' + k, v) for k, v in model_eval.items())
+            diag['times/model_eval'] = t4 - t3
         return diag
 
     # -- mopo.py:575-584: the current policy (deterministic: tanh(mu)) in the evaluation environment
@@ -220,6 +233,34 @@ class MOPO:
                               deterministic=self._eval_deterministic)
         paths = evaluation_paths(self._evaluation_environment, policy, self._eval_n_episodes, self._max_path_length)
         return evaluate_rollouts(paths, self._evaluation_environment) if paths else {}
+
+    # Philox key of the model evaluation: the run seed with this constant xor-ed in.  The training rollouts
+    # draw under the run seed itself and the SAC steps under seed + 7919 * epoch (< 2^62 for any real seed
+    # and epoch), while this constant sets bit 62: the evaluation's key never equals either, so its draws
+    # are never a training draw whatever the row, step and stream counters.
+    MODEL_EVAL_SEED_XOR = 0x6D6F64656C657661
+
+    def _evaluate_in_model(self):
+        """``model_eval_episodes`` episodes of the current policy (tanh(mu) when ``eval_deterministic``) inside
+        the learned model, from Philox-drawn env-pool rows, on the device (``ModelRollout.evaluate``).  The
+        return under the model: biased wherever the model is wrong, not a D4RL score (no perf/* keys).  Reads
+        the policy and the env pool only: the pools, the SAC state and numpy's stream are left as they are.
+        Multi-GPU: every rank runs the same evaluation (same key, uid_offset 0): replicated, no collective."""
+        if self._model_eval_episodes <= 0:
+            return {}
+        from .evaluation import model_evaluation_metrics
+        n = self._model_eval_episodes
+        if self._eval_rollout is None or self._eval_rollout.max_batch < n:
+            self._eval_rollout = ModelRollout(self._model, n, 1)
+        env_obs = self._pool.fields['observations'][:self._pool.size]
+        out = self._eval_rollout.evaluate(env_obs, self._sac.policy_params_ptr, n, self._model_eval_length,
+                                          self.fake_env.term_kind, self.fake_env.penalty_coeff,
+                                          self._model._model_inds, policy_deterministic=self._eval_deterministic,
+                                          seed=self._seed ^ self.MODEL_EVAL_SEED_XOR, epoch=self._epoch,
+                                          pi_hidden=self._pi_hidden, actor_dtype=self._actor_dtype,
+                                          penalty_learned_var=self.fake_env.penalty_learned_var,
+                                          deterministic=self._deterministic)
+        return model_evaluation_metrics(out['stats'])
 
     def train(self, n_epochs=None):
         """Generator of per-epoch diagnostics (mopo.py:650-651)."""

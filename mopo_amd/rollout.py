@@ -134,29 +134,10 @@ class ModelRollout:
         legacy = os.environ.get('MOPO_ROLLOUT_FILL') == '1'                       # A/B knob: the old launches
         alloc = torch.empty if (B > 0 and int(horizon) > 0 and not legacy) else torch.zeros
         steps = alloc(max(horizon, 1), dtype=torch.int64, device=dev)
-        ekey = (tuple(int(e) for e in np.asarray(elites).ravel()), str(dev))
-        if getattr(self, '_elites', (None, None))[0] != ekey or legacy:
-            self._elites = (ekey, torch.as_tensor(np.asarray(elites, np.int32)).to(dev))
-        el = self._elites[1]
-        keep = [steps, el]
-
-        def dptr(x, dt):
-            if x is None:
-                return None
-            t = torch.as_tensor(x).to(dev, dt).contiguous()
-            keep.append(t)
-            return L.ptr(t)
-
-        args = L.RolloutArgs(
-            d_env_obs=L.ptr(env_obs), env_size=int(env_obs.shape[0]), d_start_idx=dptr(start_idx, torch.int64),
-            d_pi_params=pi_params if isinstance(pi_params, int) else L.ptr(pi_params), pi_hidden=int(pi_hidden), d_elites=L.ptr(el), n_elites=int(el.numel()),
-            B=B, horizon=int(horizon), penalty_coeff=float(penalty_coeff), term_kind=int(term_kind),
-            seed=int(seed) & (2 ** 64 - 1), epoch=int(epoch), uid_offset=int(uid_offset),
-            d_eps_act=dptr(eps_act, torch.float32), d_eps_obs=dptr(eps_obs, torch.float64),
-            d_model_inds=dptr(model_inds, torch.int32), d_steps=L.ptr(steps),
-            penalty_learned_var=int(bool(penalty_learned_var)), deterministic=int(bool(deterministic)),
-            rollout_random=int(bool(rollout_random)), d_act_uniform=dptr(act_uniform, torch.float32),
-            actor_dtype=_ACTOR_DTYPES[actor_dtype or default_actor_dtype(self.model.dtype)])
+        keep = [steps]
+        args = self._args(keep, env_obs, pi_params, B, horizon, term_kind, penalty_coeff, elites, seed, epoch,
+                          pi_hidden, start_idx, eps_act, eps_obs, model_inds, uid_offset, steps, penalty_learned_var,
+                          deterministic, rollout_random, act_uniform, actor_dtype, legacy)
         if step_hook is not None:
             # one call per horizon step into the staging block step_hook(i) names; step_hook(i, steps)
             # is then called after step i is enqueued (multi-GPU: gather step i while i + 1 computes)
@@ -171,3 +152,68 @@ class ModelRollout:
         L.check(fn(self._h, args, desc, L.stream_ptr(stream)))
         self._keepalive = keep
         return steps[:horizon]
+
+    def _args(self, keep, env_obs, pi_params, B, horizon, term_kind, penalty_coeff, elites, seed, epoch, pi_hidden,
+              start_idx, eps_act, eps_obs, model_inds, uid_offset, steps, penalty_learned_var, deterministic,
+              rollout_random, act_uniform, actor_dtype, fresh_elites=False):
+        """The C ABI's mopo_rollout_args; every tensor it points to is appended to ``keep``."""
+        import torch
+        dev = env_obs.device
+        ekey = (tuple(int(e) for e in np.asarray(elites).ravel()), str(dev))
+        if getattr(self, '_elites', (None, None))[0] != ekey or fresh_elites:
+            self._elites = (ekey, torch.as_tensor(np.asarray(elites, np.int32)).to(dev))
+        el = self._elites[1]
+        keep.append(el)
+
+        def dptr(x, dt):
+            if x is None:
+                return None
+            t = torch.as_tensor(x).to(dev, dt).contiguous()
+            keep.append(t)
+            return L.ptr(t)
+
+        return L.RolloutArgs(
+            d_env_obs=L.ptr(env_obs), env_size=int(env_obs.shape[0]), d_start_idx=dptr(start_idx, torch.int64),
+            d_pi_params=pi_params if isinstance(pi_params, int) else L.ptr(pi_params), pi_hidden=int(pi_hidden), d_elites=L.ptr(el), n_elites=int(el.numel()),
+            B=B, horizon=int(horizon), penalty_coeff=float(penalty_coeff), term_kind=int(term_kind),
+            seed=int(seed) & (2 ** 64 - 1), epoch=int(epoch), uid_offset=int(uid_offset),
+            d_eps_act=dptr(eps_act, torch.float32), d_eps_obs=dptr(eps_obs, torch.float64),
+            d_model_inds=dptr(model_inds, torch.int32), d_steps=L.ptr(steps),
+            penalty_learned_var=int(bool(penalty_learned_var)), deterministic=int(bool(deterministic)),
+            rollout_random=int(bool(rollout_random)), d_act_uniform=dptr(act_uniform, torch.float32),
+            actor_dtype=_ACTOR_DTYPES[actor_dtype or default_actor_dtype(self.model.dtype)])
+
+    def evaluate(self, env_obs, pi_params, n_episodes, max_length, term_kind, penalty_coeff, elites,
+                 policy_deterministic=True, seed=0, epoch=0, pi_hidden=256, start_idx=None, eps_act=None,
+                 eps_obs=None, model_inds=None, uid_offset=0, stream=None, penalty_learned_var=True,
+                 deterministic=False, rollout_random=False, act_uniform=None, actor_dtype=None):
+        """Model-based policy evaluation (csrc/rollout_eval.hip): ``n_episodes`` episodes of at most
+        ``max_length`` <= 4095 steps of the policy inside the learned model, from env-pool start states, on the
+        current stream; nothing enters a pool and numpy's global stream is not drawn from.
+        ``policy_deterministic``: tanh(mu) actions (the evaluation policy, mopo.py:481-482), else sampled --
+        then the episodes are the trajectories ``run`` visits for the same arguments.  The other arguments
+        are ``run``'s.  Returns device tensors: ``returns`` (unpenalized), ``penalized_returns``,
+        ``penalty_sums`` (f64[n]), ``lengths`` (i32[n]), ``terminated`` (u8[n]), ``steps`` (int64[max_length] live
+        episodes per step) and ``stats`` (f64[16], see ``evaluation.model_evaluation_metrics``).  These are
+        returns under the model: biased wherever the model is wrong."""
+        import torch
+        dev = env_obs.device
+        n, T = int(n_episodes), int(max_length)
+        out = {'returns': torch.zeros(n, dtype=torch.float64, device=dev),
+               'penalized_returns': torch.zeros(n, dtype=torch.float64, device=dev),
+               'penalty_sums': torch.zeros(n, dtype=torch.float64, device=dev),
+               'lengths': torch.zeros(n, dtype=torch.int32, device=dev),
+               'terminated': torch.zeros(n, dtype=torch.uint8, device=dev),
+               'steps': torch.zeros(max(T, 1), dtype=torch.int64, device=dev),
+               'stats': torch.zeros(16, dtype=torch.float64, device=dev)}
+        keep = list(out.values())
+        args = self._args(keep, env_obs, pi_params, n, T, term_kind, penalty_coeff, elites, seed, epoch, pi_hidden,
+                          start_idx, eps_act, eps_obs, model_inds, uid_offset, out['steps'], penalty_learned_var,
+                          deterministic, rollout_random, act_uniform, actor_dtype)
+        ev = L.EvalArgs(policy_deterministic=int(bool(policy_deterministic)), d_return=L.ptr(out['returns']),
+                        d_pen_return=L.ptr(out['penalized_returns']), d_pen_sum=L.ptr(out['penalty_sums']),
+                        d_length=L.ptr(out['lengths']), d_terminated=L.ptr(out['terminated']),
+                        d_stats=L.ptr(out['stats']))
+        L.check(L.lib().mopo_rollout_evaluate(self._h, args, ev, L.stream_ptr(stream)))
+        self._keepalive = keep
+        return out

@@ -7,6 +7,8 @@
 ``--model-dir``: directory holding '<model_name>.mat' (bnn.py:276-281); without it the ensemble
 is trained from its initial weights to early stopping first (mopo.py:526-531).
 ``--ensemble-dtype`` / ``--actor-dtype``: the forward arithmetic (mopo_amd.bnn.DTYPES).
+``--model-eval-episodes`` / ``--model-eval-length``: evaluate the policy inside the learned model after every
+epoch (``model_eval/*``: the return under the model, not a D4RL score); off by default.
 """
 import argparse
 import json
@@ -26,6 +28,11 @@ def main(argv=None):
                         % DEFAULT_ENSEMBLE_DTYPE)
     p.add_argument('--actor-dtype', default=None, choices=('fp32', 'bf16x6', 'f16x3'),
                    help='rollout policy forward (default: the ensemble dtype for fp32 and bf16x6, else f16x3)')
+    p.add_argument('--model-eval-episodes', type=int, default=None,
+                   help='episodes of the policy inside the learned model after every epoch (model_eval/* keys; '
+                        'default: the config kwarg model_eval_episodes, else 0 = none)')
+    p.add_argument('--model-eval-length', type=int, default=None,
+                   help='step cap of those episodes, <= 4095 (default: max_path_length)')
     a = p.parse_args(argv)
     from .config import DIMS, get_params
     from .loader import restore_pool
@@ -37,6 +44,8 @@ def main(argv=None):
     pool = SimpleReplayPool(obs_dim=obs_dim, act_dim=act_dim, max_size=int(1e6))   # simple_run/base.py:267-272
     restore_pool(pool, a.data)
     over = {k: v for k, v in (('ensemble_dtype', a.ensemble_dtype), ('actor_dtype', a.actor_dtype)) if v}
+    over.update((k, v) for k, v in (('model_eval_episodes', a.model_eval_episodes),
+                                    ('model_eval_length', a.model_eval_length)) if v is not None)
     algo = from_config(params, pool, static_fns[params['domain']], model_load_dir=a.model_dir, seed=a.seed, **over)
     for diag in algo.train(a.epochs):
         print(json.dumps({k: float(v) for k, v in diag.items()}), flush=True)
