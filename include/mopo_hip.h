@@ -51,13 +51,22 @@ typedef struct mopo_bnn_s* mopo_bnn_t;
  *        4 = "f16x3": every f32 operand as 2 fp16 parts under power-of-two scales (per weight block,
  *            per activation row), 3 f16 products per f32 product, f32 accumulate (~22-bit operands,
  *            held to the fp32 parity tolerances; MOPO's default and the bench headline).
- * Limits: obs_dim + act_dim <= 64 and obs_dim <= 31 (refused here otherwise); hidden 32, 64, 200 or 400
- * (any width with the same number of 16-wide blocks); E <= 256.  Up to 32 inputs and obs_dim <= 23 (one
- * or two 16-wide input k-groups, at most 48 head slots) every dtype runs.  Wider models (e.g. ant's
- * 27 + 8) run one padded form, 64 input slots and 64 head slots: fp32 at every hidden size, bf16x6 and
- * f16x3 at hidden 32, 64 and 200 only (so e.g. hidden 33..48 or 400 with a 16-bit dtype, and bf16 / bf16x3
- * at any width, are refused here on a wide shape, with a message naming what runs). */
+ * Limits: obs_dim + act_dim <= 64 and obs_dim <= 31 (refused here otherwise); E <= 256.
+ * Hidden widths: the kernels exist for 2, 4, 8, 13, 16 and 25 hidden blocks of 16 (hidden 32, 64, 128, 200,
+ * 256, 400).  Every hidden size up to 256 runs, on the smallest of those forms that holds it (hidden 100 on
+ * 8 blocks, 220 on 16): the spare units get zero weights and biases, swish(0) = 0, so the result is exactly
+ * the logical network's; the cost is the form's (hidden 70 pays for 128).  Every API keeps the logical
+ * width.  385..400 runs in fp32 and f16x3; 257..384 and above 400 are refused here.  fp32, bf16x6 (up to 256)
+ * and f16x3 run every form; bf16 and bf16x3 keep the widths they had (up to 64, 193..208, 385..416).
+ * Up to 32 inputs and obs_dim <= 23 (one or two 16-wide input k-groups, at most 48 head slots) every dtype
+ * runs.  Wider models (e.g. ant's 27 + 8) run one padded form, 64 input slots and 64 head slots: fp32 at
+ * every hidden size above, bf16x6 and f16x3 up to hidden 208 (so e.g. hidden 256 or 400 with a 16-bit dtype,
+ * and bf16 / bf16x3 at any width, are refused here on a wide shape, with a message naming what runs). */
 int mopo_bnn_create(mopo_bnn_t* out, int E, int obs_dim, int act_dim, int hidden, int smv, int dtype);
+/* Host only: the hidden width the device form runs for a logical width (wide: obs_dim + act_dim > 32 or
+ * obs_dim > 23), or -1 where mopo_bnn_create refuses.  >= hidden, monotone in hidden, and hidden itself for
+ * every width that has a form of its own (32, 64, 128, 193..208, 256, 400). */
+int mopo_bnn_device_hidden(int hidden, int dtype, int wide);
 int mopo_bnn_destroy(mopo_bnn_t h);
 /* The reference .mat layout, keys '0'..'15' (bnn.py:224-225, 588-592): mu[1,IN], sigma[1,IN],
  * (W[E,in,out], b[E,1,out]) x 5 mean layers, (Wv[E,H,D], bv[E,1,D]) if smv, maxlv[1,D], minlv[1,D].
@@ -123,10 +132,16 @@ int mopo_actor_forward(const float* d_pi_params, int obs_dim, int act_dim, int h
                        uint64_t seed, uint32_t step, float* d_act, float* d_mu, void* stream);
 /* The same with the arithmetic chosen: dtype 0 = fp32 (f32 MFMA), 3 = bf16x6 (f32 operands split exactly into
  * 3 bf16 parts, 6 bf16 MFMA products), 4 = f16x3 (f32 operands as 2 fp16 parts under power-of-two scales,
- * 3 f16 MFMA products, ~22-bit operands); hidden 32 or 256 for the split forms. */
+ * 3 f16 MFMA products, ~22-bit operands).  hidden: the parameter stride, any width up to 256; the kernels run
+ * the next multiple of 32 (mopo_actor_device_hidden) with the spare units' weights and biases zero, which is
+ * exact for the relu layers.  32 and 256 run the kernels they always ran. */
 int mopo_actor_forward_dtype(const float* d_pi_params, int obs_dim, int act_dim, int hidden,
                              const void* d_obs, int obs_f64, int64_t B, const float* d_eps,
                              uint64_t seed, uint32_t step, float* d_act, float* d_mu, int dtype, void* stream);
+
+/* Host only: the hidden width the actor kernels run for a policy of width hidden in this dtype (0, 3 or 4), or
+ * -1 (hidden outside [1, 256], another dtype).  >= hidden, monotone, the identity on multiples of 32. */
+int mopo_actor_device_hidden(int hidden, int dtype);
 
 /* ---- device-resident SimpleReplayPool ---------------------------------------------------
  * SoA fields (simple_replay_pool.py:48-70), all caller-owned device arrays of max_size rows:

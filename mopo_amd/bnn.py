@@ -117,6 +117,49 @@ def parse_structure(path):
     return layers
 
 
+def device_hidden(hidden, dtype='fp32', wide=False):
+    """The hidden width the device form runs for a logical width (csrc/internal.h ``bnn_form_blocks``): ``hidden``
+    itself where it has a form of its own, the next form's width otherwise (100 -> 128, 220 -> 256), -1 where
+    ``mopo_bnn_create`` refuses.  The library answers; nothing here restates the rule."""
+    return int(L.lib().mopo_bnn_device_hidden(int(hidden), _DTYPES[dtype], int(bool(wide))))
+
+
+def _hidden_axes(n):
+    """(array index, axis) pairs of the .mat layout (16 smv / 14 joint arrays) that run over the hidden width."""
+    ax = [(2, 2), (3, 2)]
+    for i in (4, 6, 8):
+        ax += [(i, 1), (i, 2), (i + 1, 2)]
+    ax.append((10, 1))
+    if n == 16:
+        ax.append((12, 1))
+    return ax
+
+
+def embed_hidden(mats, hidden_to):
+    """The .mat arrays of a width-H ensemble as those of a width-``hidden_to`` one computing exactly the same
+    function: the extra units get zero incoming and outgoing weights and zero biases (swish(0) = 0).  This is the
+    embedding the device packer applies when a logical width runs on a wider form; here it is stated on the .mat
+    layout, for the oracle and the tests."""
+    mats = [np.asarray(m) for m in mats]
+    out = list(mats)
+    H = mats[2].shape[2]
+    if hidden_to < H:
+        raise ValueError('embed_hidden: %d units do not fit %d' % (H, hidden_to))
+    for i, axis in _hidden_axes(len(mats)):
+        pad = [(0, 0)] * out[i].ndim
+        pad[axis] = (0, hidden_to - H)
+        out[i] = np.pad(out[i], pad)
+    return out
+
+
+def extract_hidden(mats, hidden):
+    """The inverse of ``embed_hidden``: the first ``hidden`` units of every hidden axis."""
+    out = [np.asarray(m) for m in mats]
+    for i, axis in _hidden_axes(len(out)):
+        out[i] = np.ascontiguousarray(np.take(out[i], np.arange(hidden), axis=axis))
+    return out
+
+
 def _smv_shapes(shapes):
     """.mat shapes of the smv layout for a (joint or smv) list of shapes."""
     if len(shapes) == 16:

@@ -37,7 +37,13 @@ struct ActorArgs {
   int alone;
 };
 
+// The kernels run hidden widths that are multiples of 32 (the 16-bit forms' 32-deep k-groups; the f32 form follows
+// the same rule): a policy of width Hp (the SAC parameter stride, any value up to 256) is zero-embedded into the
+// next multiple by pack_actor -- zero incoming weights and biases, relu(0) = 0, zero outgoing weights: exact.
+__host__ __device__ constexpr int actor_kernel_hidden(int Hp) { return (Hp + 31) / 32 * 32; }
+
 int launch_actor(const ActorArgs& a, hipStream_t s);
+int launch_actor_widths(const ActorArgs& a, hipStream_t s);   // actor_widths.hip: kernel widths 64 .. 224
 __host__ __device__ int64_t actor_packed_floats(int O, int Hp, int split = 0);
 int pack_actor(const float* P, int O, int A, int Hp, float* dst, hipStream_t s, int split = 0);
 

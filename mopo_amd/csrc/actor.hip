@@ -12,6 +12,7 @@
 
 namespace mopo {
 
+#ifndef MOPO_ACTOR_TEMPLATES_ONLY   // actor_widths.hip includes this file for the kernel templates below only
 // packed layout: W1 frags | W2 frags | head frags | b1 [NB*16] | b2 [NB*16] | [bmu | bls] [16]
 // (biases zero-padded to whole 16-blocks so the kernel stages them into LDS with global_load_lds)
 // f16 (f16x3): W1 [1][2][NB] | W2 [NB/2][2][NB] | head [NB/2][2][1] fragments of 64 lanes x 8 fp16
@@ -22,7 +23,7 @@ constexpr int WMAX_BLOCKS = 64;   // actor_wmax_kernel's grid (<= 64: one wave r
 // split: 0 f32 fragments, 1 f16x3 (2 scaled fp16 parts), 2 bf16x6 (the exact 3-part bf16 split, no scales):
 // W1 [1][3][NB] | W2 [NB/2][3][NB] | head [NB/2][3][1] fragments, then the biases
 __host__ __device__ int64_t actor_packed_floats(int O, int Hp, int split) {
-  const int KG0 = (O + 15) / 16, NB = (Hp + 15) / 16;
+  const int KG0 = (O + 15) / 16, NB = actor_kernel_hidden(Hp) / 16;
   if (split == 2) return (int64_t)(3 * NB + 3 * (NB / 2) * NB + 3 * (NB / 2)) * 256 + 2LL * NB * 16 + 16;
   if (split) return (int64_t)(2 * NB + NB * NB + NB) * 256 + 2LL * NB * 16 + 16 + 8 + 3 * WMAX_BLOCKS;
   return (int64_t)KG0 * NB * 256 + (int64_t)NB * NB * 256 + (int64_t)NB * 256 + 2LL * NB * 16 + 16;
@@ -62,7 +63,7 @@ __global__ __launch_bounds__(256) void actor_wmax_kernel(const float* __restrict
 // biases as in the f32 packing, and the 3 inverse scales
 __global__ void pack_actor_f16_kernel(const float* __restrict__ P, int O, int A, int Hp, float* __restrict__ dst,
                                       const float* __restrict__ wpart) {
-  const int NB = ceil_div(Hp, 16), KG = NB / 2;
+  const int NB = actor_kernel_hidden(Hp) / 16, KG = NB / 2;
   const float* W1 = P;
   const float* W2 = W1 + O * Hp + Hp;
   const float* Wm = W2 + Hp * Hp + Hp;
@@ -126,7 +127,7 @@ __global__ void pack_actor_f16_kernel(const float* __restrict__ P, int O, int A,
 // (k permutation of the ensemble's), [kg][p][nb] per matrix; the biases as in the f32 packing
 __global__ void pack_actor_x6_kernel(const float* __restrict__ P, int O, int A, int Hp, float* __restrict__ dst) {
   constexpr int NP = 3;
-  const int NB = ceil_div(Hp, 16), KG = NB / 2;
+  const int NB = actor_kernel_hidden(Hp) / 16, KG = NB / 2;
   const float* W1 = P;
   const float* W2 = W1 + O * Hp + Hp;
   const float* Wm = W2 + Hp * Hp + Hp;
@@ -177,7 +178,7 @@ __global__ void pack_actor_x6_kernel(const float* __restrict__ P, int O, int A, 
 // W1 (observation side in slot_feat order), W2, the combined head (n < A -> Wmu[:, n],
 // A <= n < 2A -> Wls[:, n - A]) fragment-major (mlp_tile.h), then the zero-padded biases.
 __global__ void pack_actor_kernel(const float* __restrict__ P, int O, int A, int Hp, float* __restrict__ dst) {
-  const int KG0 = ceil_div(O, 16), NB = ceil_div(Hp, 16);
+  const int KG0 = ceil_div(O, 16), NB = actor_kernel_hidden(Hp) / 16;
   const float* W1 = P;
   const float* W2 = W1 + O * Hp + Hp;
   const float* Wm = W2 + Hp * Hp + Hp;
@@ -217,8 +218,8 @@ __global__ void pack_actor_kernel(const float* __restrict__ P, int O, int A, int
 }
 
 int pack_actor(const float* P, int O, int A, int Hp, float* dst, hipStream_t s, int split) {
+  MOPO_REQUIRE(Hp >= 1 && Hp <= 256, "actor: hidden width must be in [1, 256]");
   if (split == 2) {
-    MOPO_REQUIRE(Hp % 32 == 0, "actor bf16x6: hidden width must be a multiple of 32");
     MOPO_REQUIRE(O <= 32 && 2 * A <= 16, "actor bf16x6: obs_dim <= 32, act_dim <= 8");
     const int64_t tot = actor_packed_floats(O, Hp, 2) * 2;   // upper bound on the elements the kernel walks
     hipLaunchKernelGGL(pack_actor_x6_kernel, dim3((int)std::min<int64_t>((tot + 255) / 256, 1024)), dim3(256), 0, s,
@@ -228,9 +229,8 @@ int pack_actor(const float* P, int O, int A, int Hp, float* dst, hipStream_t s, 
   }
   const int f16 = split;
   if (f16) {
-    MOPO_REQUIRE(Hp % 32 == 0, "actor f16x3: hidden width must be a multiple of 32");
     MOPO_REQUIRE(O <= 32 && 2 * A <= 16, "actor f16x3: obs_dim <= 32, act_dim <= 8");
-    const int NB = Hp / 16;
+    const int NB = actor_kernel_hidden(Hp) / 16;
     float* wpart = dst + (2LL * NB + NB * NB + NB) * 256 + 2LL * NB * 16 + 16 + 8;
     hipLaunchKernelGGL(actor_wmax_kernel, dim3(WMAX_BLOCKS), dim3(256), 0, s, P, O, A, Hp, wpart);
     MOPO_HIP(hipGetLastError());
@@ -246,6 +246,7 @@ int pack_actor(const float* P, int O, int A, int Hp, float* dst, hipStream_t s, 
   MOPO_HIP(hipGetLastError());
   return 0;
 }
+#endif  // MOPO_ACTOR_TEMPLATES_ONLY
 
 // bias (staged in LDS by layer_lds) + relu
 template <int NB>
@@ -873,6 +874,9 @@ __global__ __launch_bounds__(ACT_WAVES * 64, 2) void actor_f16q_kernel(const Act
 }
 #endif
 
+#ifdef MOPO_ACTOR_TEMPLATES_ONLY
+}  // namespace mopo
+#else
 int launch_actor(const ActorArgs& a, hipStream_t s) {
   if (a.B == 0) return 0;
   MOPO_REQUIRE(!a.xs || (a.xs_mu && a.xs_sigma && a.xs_in == a.O + a.A && a.xs_in <= XS_STRIDE),
@@ -880,46 +884,50 @@ int launch_actor(const ActorArgs& a, hipStream_t s) {
   MOPO_REQUIRE(a.A >= 1 && 2 * a.A <= 16, "actor: act_dim must be in [1, 8]");
   MOPO_REQUIRE(a.O >= 1 && a.O <= 32, "actor: obs_dim must be in [1, 32]");
   MOPO_REQUIRE(a.Wpk, "actor: packed weights required");
+  MOPO_REQUIRE(a.Hp >= 1 && a.Hp <= 256, "actor: hidden width must be in [1, 256]");
+  // every width but the two product ones (32, 256: the kernels below) runs in actor_widths.hip
+  if (actor_kernel_hidden(a.Hp) != 256 && actor_kernel_hidden(a.Hp) != 32) return launch_actor_widths(a, s);
+  const int Hk = actor_kernel_hidden(a.Hp);
   dim3 grid(ceil_div((int)a.B, 16 * ACT_WAVES)), block(64 * ACT_WAVES);
 #if ACT_F16_R > 0
   if (a.dtype == DT_F16X3) {
     constexpr int R = ACT_F16_R;
     const dim3 gr(ceil_div((int)a.B, 16 * ACT_WAVES * R));
-    if (a.Hp == 256) hipLaunchKernelGGL((actor_f16r_kernel<16, R>), gr, block, 0, s, a);
-    else if (a.Hp == 32) hipLaunchKernelGGL((actor_f16r_kernel<2, R>), gr, block, 0, s, a);
+    if (Hk == 256) hipLaunchKernelGGL((actor_f16r_kernel<16, R>), gr, block, 0, s, a);
+    else if (Hk == 32) hipLaunchKernelGGL((actor_f16r_kernel<2, R>), gr, block, 0, s, a);
     else return fail("actor f16x3: unsupported hidden size (256 or 32)");
     MOPO_HIP(hipGetLastError());
     return 0;
   }
 #endif
   if (a.dtype == DT_BF16X6) {
-    if (a.Hp == 256) hipLaunchKernelGGL(actor_x6_kernel<16>, grid, block, 0, s, a);
-    else if (a.Hp == 32) hipLaunchKernelGGL(actor_x6_kernel<2>, grid, block, 0, s, a);
+    if (Hk == 256) hipLaunchKernelGGL(actor_x6_kernel<16>, grid, block, 0, s, a);
+    else if (Hk == 32) hipLaunchKernelGGL(actor_x6_kernel<2>, grid, block, 0, s, a);
     else return fail("actor bf16x6: unsupported hidden size (256 or 32)");
     MOPO_HIP(hipGetLastError());
     return 0;
   }
   if (a.dtype == DT_F16X3) {
 #if ACT_F16_RING
-    if (a.alone && a.Hp == 256) hipLaunchKernelGGL(actor_f16q_kernel<16>, grid, block, 0, s, a);
+    if (a.alone && Hk == 256) hipLaunchKernelGGL(actor_f16q_kernel<16>, grid, block, 0, s, a);
     else
 #endif
-    if (a.Hp == 256) hipLaunchKernelGGL(actor_f16_kernel<16>, grid, block, 0, s, a);
-    else if (a.Hp == 32) hipLaunchKernelGGL(actor_f16_kernel<2>, grid, block, 0, s, a);
+    if (Hk == 256) hipLaunchKernelGGL(actor_f16_kernel<16>, grid, block, 0, s, a);
+    else if (Hk == 32) hipLaunchKernelGGL(actor_f16_kernel<2>, grid, block, 0, s, a);
     else return fail("actor f16x3: unsupported hidden size (256 or 32)");
     MOPO_HIP(hipGetLastError());
     return 0;
   }
   const int KG0 = ceil_div(a.O, 16);
-  if (a.Hp == 256 && KG0 == 2 && tail_steps(a.O) == 1)  // halfcheetah / walker2d: 17 = 16 + 1
+  if (Hk == 256 && KG0 == 2 && tail_steps(a.O) == 1)  // halfcheetah / walker2d: 17 = 16 + 1
     hipLaunchKernelGGL((actor_kernel<2, 16, 1>), grid, block, 0, s, a);
-  else if (a.Hp == 256 && KG0 == 2)
+  else if (Hk == 256 && KG0 == 2)
     hipLaunchKernelGGL((actor_kernel<2, 16>), grid, block, 0, s, a);
-  else if (a.Hp == 256 && KG0 == 1)
+  else if (Hk == 256 && KG0 == 1)
     hipLaunchKernelGGL((actor_kernel<1, 16>), grid, block, 0, s, a);
-  else if (a.Hp == 32 && KG0 == 2)
+  else if (Hk == 32 && KG0 == 2)
     hipLaunchKernelGGL((actor_kernel<2, 2>), grid, block, 0, s, a);
-  else if (a.Hp == 32 && KG0 == 1)
+  else if (Hk == 32 && KG0 == 1)
     hipLaunchKernelGGL((actor_kernel<1, 2>), grid, block, 0, s, a);
   else
     return fail("actor: unsupported hidden size (256 or 32)");
@@ -930,6 +938,11 @@ int launch_actor(const ActorArgs& a, hipStream_t s) {
 }  // namespace mopo
 
 using namespace mopo;
+
+extern "C" int mopo_actor_device_hidden(int hidden, int dtype) {
+  if (hidden < 1 || hidden > 256 || !(dtype == DT_FP32 || dtype == DT_F16X3 || dtype == DT_BF16X6)) return -1;
+  return actor_kernel_hidden(hidden);
+}
 
 extern "C" int64_t mopo_sac_param_count(int O, int A, int H) {
   int64_t pi = (int64_t)O * H + H + (int64_t)H * H + H + 2 * ((int64_t)H * A + A);
@@ -967,3 +980,4 @@ extern "C" int mopo_actor_forward(const float* P, int O, int A, int H, const voi
                                   void* stream) {
   return mopo_actor_forward_dtype(P, O, A, H, obs, obs_f64, B, eps, seed, step, act, mu, DT_FP32, stream);
 }
+#endif  // MOPO_ACTOR_TEMPLATES_ONLY

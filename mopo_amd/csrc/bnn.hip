@@ -26,9 +26,10 @@
 
 namespace mopo {
 
+#ifndef MOPO_BNN_TEMPLATES_ONLY   // bnn_widths*.hip include this file for the kernel templates below only
 static const char* const kWide16Msg =
-    "bnn: a wide model (obs_dim + act_dim > 32 or obs_dim > 23) runs in fp32 at hidden 32, 64, 200 or 400 and in "
-    "bf16x6 / f16x3 at hidden 32, 64 or 200 (the widths with the same number of 16-wide blocks); bf16, bf16x3 and "
+    "bnn: a wide model (obs_dim + act_dim > 32 or obs_dim > 23) runs in fp32 at every hidden size up to 256 and at "
+    "385..400, and in bf16x6 / f16x3 at every hidden size up to 208; bf16, bf16x3 and "
     "other hidden sizes are not supported there";
 
 // ---------------------------------------------------------------------------------------
@@ -150,6 +151,7 @@ int pack_frags(const float* src, float* dst, int E, int K, int N, int KG, int NB
   MOPO_HIP(hipGetLastError());
   return 0;
 }
+#endif  // MOPO_BNN_TEMPLATES_ONLY
 
 __device__ __forceinline__ float load_feat(const void* p, int f64, int64_t idx) {
   return f64 ? (float)reinterpret_cast<const double*>(p)[idx] : reinterpret_cast<const float*>(p)[idx];
@@ -951,6 +953,21 @@ __global__ __launch_bounds__(WAVES * 64, R == 1 ? 2 : 1) void bnn_fwd_f16r_kerne
 #ifndef BNN_RING_MINB_X6
 #define BNN_RING_MINB_X6 3  // the same for bf16x6 (P = 3)
 #endif
+// bf16x6 at 16 hidden blocks (H = 209..256) has knobs of its own: at the 168-VGPR cap of 3 workgroups per CU it
+// spills at every prefetch depth (3 reads in flight: 40 B per lane in the rollout form, 2: 20-28 B, 1: 8-12 B);
+// capped for 2 workgroups per CU it takes 185 (3 in flight) or 177 (2) VGPRs and no scratch
+#ifndef BNN_RING_PF_X6_16
+#define BNN_RING_PF_X6_16 3
+#endif
+#ifndef BNN_RING_MINB_X6_16
+#define BNN_RING_MINB_X6_16 2
+#endif
+// workgroups per CU the ring kernel's registers are capped for
+template <int NB2, int P, int WAVES>
+constexpr int ring_minb() {
+  const int b = (P == 3 ? (NB2 == 16 ? BNN_RING_MINB_X6_16 : BNN_RING_MINB_X6) : BNN_RING_MINB) * 4 / WAVES;
+  return b > 0 ? b : 1;
+}
 // KG0B: 32-deep k-groups of the input row (2: wide models, up to 64 inputs; layer 0 then owns P KG0B slices,
 // w0b is [E][KG0B][P][NB2] and the xs rows lie 32 KG0B floats apart)
 // KP (internal.h bnn_kpack; bf16x6, H = 197..200): the last k-group of every hidden-width input, 2 real values per
@@ -958,9 +975,7 @@ __global__ __launch_bounds__(WAVES * 64, R == 1 ? 2 : 1) void bnn_fwd_f16r_kerne
 // two MFMAs per block (the second half full) -- instead of P slices and P (P + 1) / 2 half-zero 16-deep MFMAs.
 // Every product is the same exact bf16 x bf16 one; only the f32 accumulation order of that k-group differs.
 template <int NB2, int NBO, int MODE, int WAVES, int P, int DEPTH, int NBU = NB2, int KG0B = 1, bool KP = false>
-__global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_MINB) * 4 / WAVES > 0)
-                                             ? (P == 3 ? BNN_RING_MINB_X6 : BNN_RING_MINB) * 4 / WAVES : 1) void bnn_fwd_ring_kernel(const BnnDev w,
-                                                                                            const FwdArgs a) {
+__global__ __launch_bounds__(WAVES * 64, (ring_minb<NB2, P, WAVES>())) void bnn_fwd_ring_kernel(const BnnDev w, const FwdArgs a) {
   static_assert(P == 1 || P == 2 || P == 3, "1: bf16, 2: f16x3, 3: bf16x6 (the exact 3-part bf16 split)");
   static_assert(DEPTH >= 3, "ring of at least 3 slots");
   constexpr bool F16 = P == 2;
@@ -1225,7 +1240,7 @@ __global__ __launch_bounds__(WAVES * 64, ((P == 3 ? BNN_RING_MINB_X6 : BNN_RING_
       auto frag = [&](int i) { return *reinterpret_cast<const bf16x8*>(b + (((i / NBUL) * NBL + i % NBUL) * 64 + lane) * 4); };
       // fragments read BNN_RING_PF ahead of their MFMAs, each read pinned ahead of the MFMAs that follow it
       // (left to itself the scheduler sinks it to just before its use: an exposed LDS latency per pair)
-      constexpr int PF = P == 3 ? BNN_RING_PF_X6 : BNN_RING_PF, NFR = REM ? NBUL : PPS * NBUL;
+      constexpr int PF = P == 3 ? (NB2 == 16 ? BNN_RING_PF_X6_16 : BNN_RING_PF_X6) : BNN_RING_PF, NFR = REM ? NBUL : PPS * NBUL;
       bf16x8 fq[PF];
 #pragma unroll
       for (int k = 0; k < PF; ++k)
@@ -1316,7 +1331,7 @@ static int launch_ring(const Bnn* h, int mode, FwdArgs a, hipStream_t s) {
 template <int NB2>
 static bool ring_shape(const Bnn* h) { return NB2 <= 16 && (NB2 == 14 ? h->dev.NBH == 13 : h->dev.NBH == NB2); }
 // the packed remainder's weight layout (set_params packs by the same predicate): the ring kernel's KP form only
-static bool kpack_shape(const Bnn* h) { return bnn_kpack(h->dtype, h->dev.NB2, h->dev.NBH, h->H); }
+static inline bool kpack_shape(const Bnn* h) { return bnn_kpack(h->dtype, h->dev.NB2, h->dev.NBH, h->HD); }
 // bf16x6 on the ring: the packed-remainder form where the weights are packed for it (H = 197..200)
 template <int NB2, int NBO, int KG0B = 1>
 static int launch_ring_x6(const Bnn* h, int mode, const FwdArgs& a, hipStream_t s) {
@@ -1349,6 +1364,9 @@ static int launch_fwd_t(const Bnn* h, int mode, FwdArgs a, hipStream_t s) {
   return 0;
 }
 
+#ifdef MOPO_BNN_TEMPLATES_ONLY
+}  // namespace mopo
+#else
 template <int KG0, int NBO>
 static int launch_fwd_h(const Bnn* h, int mode, const FwdArgs& a, hipStream_t s) {
   switch (h->dev.NBH) {
@@ -1356,7 +1374,7 @@ static int launch_fwd_h(const Bnn* h, int mode, const FwdArgs& a, hipStream_t s)
     case 4: return launch_fwd_t<KG0, 4, NBO, 2>(h, mode, a, s);
     case 13:  // H = 200 with 17 + 6 inputs (every halfcheetah / walker2d config): skip the padding k-steps
       if constexpr (KG0 <= 2)   // the wide form (KG0 = 4) has the whole-k-group variant only
-        if (KG0 == 2 && NBO == 3 && tail_steps(h->dev.IN) <= 2 && tail_steps(h->H) <= 2)
+        if (KG0 == 2 && NBO == 3 && tail_steps(h->dev.IN) <= 2 && tail_steps(h->HD) <= 2)
           return launch_fwd_t<KG0, 13, NBO, BNN_R13, 2, 2>(h, mode, a, s);
       return launch_fwd_t<KG0, 13, NBO, BNN_R13>(h, mode, a, s);
     case 25:
@@ -1537,6 +1555,7 @@ static int launch_bf16(const Bnn* h, int mode, const FwdArgs& a, hipStream_t s) 
 
 int launch_bnn_fwd(const Bnn* h, int mode, const FwdArgs& a, hipStream_t s) {
   if (!h->has_params) return fail("bnn: parameters not set (mopo_bnn_set_params)");
+  if (h->dev.NBH == 8 || h->dev.NBH == 16) return launch_bnn_fwd_widths(h, mode, a, s);
   if (h->dtype != 0) return launch_bf16(h, mode, a, s);
   // wide models: one form per hidden width, 4 input k-groups and 4 head blocks (unused ones are zero padding)
   if (h->dev.KG0 == 4 && h->dev.NBO == 4) return launch_fwd_h<4, 4>(h, mode, a, s);
@@ -1578,21 +1597,43 @@ extern "C" int mopo_bnn_create(mopo_bnn_t* out, int E, int obs_dim, int act_dim,
   d.NB2 = (d.NBH + 1) / 2 * 2;
   d.BS = d.NB2 * 16;
   if (wide && dtype != DT_FP32 &&
-      !((dtype == DT_BF16X6 || dtype == DT_F16X3) && ((d.NB2 == 14 && d.NBH == 13) || (d.NB2 == 4 && d.NBH == 4) || d.NBH == 2))) {
+      !((dtype == DT_BF16X6 || dtype == DT_F16X3) && d.NBH <= 13)) {   // every width up to 208 has a 16-bit ring form
     delete h;
     return fail(std::string("mopo_bnn_create: ") + kWide16Msg);
   }
-  if (dtype != 0 && d.NB2 == 14 && d.NBH != 13) {   // the 16-bit kernels' NB2 = 14 shape is H = 200's 13 blocks
+  // the 16-bit kernels' NB2 = 14 shape is H = 200's 13 blocks: bf16x6 / f16x3 run 209..224 on 16 blocks
+  if ((dtype == DT_BF16 || dtype == DT_BF16X3) && d.NB2 == 14 && d.NBH != 13) {
     delete h;
-    return fail("mopo_bnn_create: the 16-bit dtypes do not support hidden sizes 209..224 (got " +
-                std::to_string(hidden) + "; use fp32)");
+    return fail("mopo_bnn_create: bf16 and bf16x3 do not support hidden sizes 209..224 (got " +
+                std::to_string(hidden) + "; use fp32, bf16x6 or f16x3)");
   }
   if (dtype == 3 && d.NB2 > 16) {   // launch_bf16_t: no bf16x6 kernel above H = 256
     delete h;
     return fail("mopo_bnn_create: bf16x6 supports hidden sizes <= 256 (use f16x3 or fp32)");
   }
+  // the form that runs this width (internal.h bnn_form_blocks): its own where it has one, else the smallest that
+  // holds it; the packer fills the form's spare units with zeros
+  const int form = bnn_form_blocks(hidden, dtype, wide);
+  if (form < 0) {
+    delete h;
+    if (dtype == DT_BF16 || dtype == DT_BF16X3)
+      return fail("mopo_bnn_create: bf16 and bf16x3 run hidden sizes up to 64, 193..208 and 385..416 only (got " +
+                  std::to_string(hidden) + "; fp32, bf16x6 and f16x3 run every hidden size up to 256)");
+    return fail("mopo_bnn_create: no kernel for hidden size " + std::to_string(hidden) +
+                " (every hidden size up to 256 runs in fp32, bf16x6 and f16x3, 385..400 in fp32 and f16x3; a wide "
+                "model's bf16x6 / f16x3 stop at 208)");
+  }
+  h->HD = bnn_device_hidden(hidden, dtype, wide);
+  d.NBH = form;
+  d.NB2 = (d.NBH + 1) / 2 * 2;
+  d.BS = d.NB2 * 16;
   *out = reinterpret_cast<mopo_bnn_t>(h);
   return 0;
+}
+
+extern "C" int mopo_bnn_device_hidden(int hidden, int dtype, int wide) {
+  if (dtype < 0 || dtype > 4) return -1;
+  return bnn_device_hidden(hidden, dtype, wide != 0);
 }
 
 extern "C" int mopo_bnn_destroy(mopo_bnn_t hh) {
@@ -1701,7 +1742,7 @@ extern "C" int mopo_bnn_set_params(mopo_bnn_t hh, const float* const* arrs, int 
     // KG0B = the input's 32-deep k-groups: 1, wide models (KG0 = 4) 2
     const int NB2 = d.NB2, KG = NB2 / 2, P = bf16_parts(h->dtype), KG0B = (KG0 + 1) / 2;
     // bnn_kpack: the hidden-width inputs' last k-group is ONE packed slice behind the KG - 1 full ones' P
-    const bool kpack = bnn_kpack(h->dtype, NB2, NBH, H);
+    const bool kpack = bnn_kpack(h->dtype, NB2, NBH, h->HD);
     const int64_t SLM = kpack ? (KG - 1) * P + 1 : KG * P;   // slices per member of a hidden-width input
     const int64_t f0 = (int64_t)E * KG0B * P * NB2, fh = 3LL * E * SLM * NB2, fd = (int64_t)E * SLM * NBO;
     if (!h->bbuf) MOPO_HIP(hipMalloc(&h->bbuf, (f0 + fh + fd) * 256 * sizeof(float)));
@@ -1819,3 +1860,4 @@ extern "C" int mopo_bnn_packed_copy(mopo_bnn_t hh, int to_handle, void* d_buf, i
   }
   return 0;
 }
+#endif  // MOPO_BNN_TEMPLATES_ONLY

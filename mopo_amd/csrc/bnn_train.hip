@@ -445,7 +445,7 @@ bool use_rows(const Train* h) {
   }();
   const Layout& L = h->L;
   const int g0 = ceil_div(L.IN, 16), gh = ceil_div(L.H, 16), gd = ceil_div(2 * L.D, 16);
-  const bool inst = ((gh == 13 || gh == 16 || gh == 2) && ((g0 == 2 && gd == 3) || (g0 == 1 && gd == 2))) ||
+  const bool inst = ((gh == 13 || gh == 16 || gh == 8 || gh == 2) && ((g0 == 2 && gd == 3) || (g0 == 1 && gd == 2))) ||
                     ((gh == 13 || gh == 4) && g0 == 3 && gd == 4);   // step_rows' lists; the last: ant-sized rows
   return env != 0 && inst && L.H % 4 == 0 && L.D % 2 == 0;
 }
@@ -832,6 +832,7 @@ int step_rows(Train* h, int par, const float* in, const float* tg, const int32_t
     } else
     MOPO_TRF(2, 13, 3) MOPO_TRF(1, 13, 2) MOPO_TRF(1, 2, 2) MOPO_TRF(2, 2, 3) MOPO_TRF(2, 16, 3) MOPO_TRF(1, 16, 2)
     MOPO_TRF(3, 13, 4) MOPO_TRF(3, 4, 4)   // ant-sized rows: 27 + 8 inputs, 56 head columns
+    MOPO_TRF(2, 8, 3) MOPO_TRF(1, 8, 2)   // H = 113..128
     return fail("bnn train: no row-block instantiation for these widths (use_rows)");
 #undef MOPO_TRF
     // on this path h->G holds only the max/min log-var gradients (train_rows.h loss tail); the W/b
@@ -897,6 +898,7 @@ int step_rows(Train* h, int par, const float* in, const float* tg, const int32_t
   } else
   MOPO_TRR(2, 13, 3) MOPO_TRR(1, 13, 2) MOPO_TRR(1, 2, 2) MOPO_TRR(2, 2, 3) MOPO_TRR(2, 16, 3) MOPO_TRR(1, 16, 2)
     MOPO_TRR(3, 13, 4) MOPO_TRR(3, 4, 4)   // ant-sized rows: 27 + 8 inputs, 56 head columns
+    MOPO_TRR(2, 8, 3) MOPO_TRR(1, 8, 2)   // H = 113..128
   return fail("bnn train: no row-block instantiation for these widths (use_rows)");
 #undef MOPO_TRR
   std::vector<GemmProb> g;

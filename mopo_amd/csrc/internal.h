@@ -53,8 +53,48 @@ __host__ __device__ constexpr bool bnn_kpack(int dtype, int NB2, int NBH, int H)
   return dtype == DT_BF16X6 && NB2 == 14 && NBH == 13 && tail_steps(H) == 2;
 }
 
+// ---- hidden-width forms --------------------------------------------------------------------------------------
+// The forward kernels exist for a few hidden-block counts ("forms"): 2, 4, 8, 13, 16 and 25 blocks of 16.  A
+// logical hidden width H with no form of its own runs on the smallest form that holds it: the packer
+// (mopo_bnn_set_params) lays the H real units into the form's slots (slot_feat) and fills the rest with zero
+// weights and biases, and swish(0) = 0, so the padded units contribute exact zeros.  Every API keeps H.
+// Returns the form's block count for (H, dtype, wide), or -1 where no kernel runs it.  The forms of 8 and 16
+// blocks are bnn_widths.hip's; block counts that ran before they existed keep the kernel they had.
+inline int bnn_form_blocks(int hidden, int dtype, bool wide) {
+  if (hidden < 1) return -1;
+  const int nb = (hidden + 15) / 16;
+  const bool split = dtype == 3 /* bf16x6 */ || dtype == 4 /* f16x3 */;
+  if (!wide && dtype != 0) {
+    // odd counts the non-ring 16-bit kernels take as they are (their NBU = NB2 - 1 forms), and 26 whole blocks
+    if (dtype != 4 && (nb == 1 || nb == 3)) return nb;
+    if (dtype != 3 && nb == 26) return nb;
+    if (!split) return (nb == 2 || nb == 4 || nb == 13 || nb == 25) ? nb : -1;   // bf16, bf16x3: no new forms
+  }
+  if (wide && dtype != 0 && !split) return -1;
+  const int forms[6] = {2, 4, 8, 13, 16, 25};
+  // 16-bit limits: bf16x6 has no form above 16 blocks, a wide model none above 13
+  const int top = dtype == 0 ? 25 : (wide ? 13 : (dtype == 3 ? 16 : 25));
+  for (int f : forms)
+    if (f >= nb && f <= top) return (f == 25 && nb < 25) ? -1 : f;   // H = 257..384: refused, not run at 400's cost
+  return -1;
+}
+// The width the device form runs for a logical width: H itself where H lies in the last block of a form that
+// takes partial blocks (every width that ran before the 8- and 16-block forms existed), otherwise the form's
+// smallest own width (whole blocks for the forms of 8 and 16).  Monotone in H, >= H, -1 where refused.
+inline int bnn_device_hidden(int hidden, int dtype, bool wide) {
+  const int f = bnn_form_blocks(hidden, dtype, wide);
+  if (f < 0) return -1;
+  const int lo = (f == 8 || f == 16) ? 16 * f : 16 * (f - 1) + 1;
+  return hidden > lo ? hidden : lo;
+}
+
+static const char* const kWidths16Msg =
+    "bnn: hidden sizes 65..128 and 209..256 run in fp32, bf16x6 and f16x3 (a wide model -- obs_dim + act_dim > 32 or "
+    "obs_dim > 23 -- in fp32, and up to 128 in bf16x6 / f16x3); bf16 and bf16x3 are not supported there";
+
 struct Bnn {
   int E, O, A, H, smv, dtype;
+  int HD = 0;  // bnn_device_hidden(H): the width the tail-skipping and packed-remainder choices are made from
   bool has_params = false;
   float* buf = nullptr;      // one device allocation for all packed params
   uint16_t* bbuf = nullptr;  // bf16 packed weights
@@ -100,6 +140,9 @@ struct FwdArgs {
 };
 
 int launch_bnn_fwd(const Bnn* h, int mode, const FwdArgs& a, hipStream_t s);
+// the forms of 8 and 16 hidden blocks (bnn_widths.hip: fp32; bnn_widths16.hip: bf16x6, f16x3)
+int launch_bnn_fwd_widths(const Bnn* h, int mode, const FwdArgs& a, hipStream_t s);
+int launch_bnn_fwd_widths16(const Bnn* h, int mode, const FwdArgs& a, hipStream_t s);
 // W[E][K][N] (TF layout) -> fragment-major (see BnnDev) on stream s
 // perm_k: the K side is an input width in slot_feat order (mlp_tile.h)
 int pack_frags(const float* src, float* dst, int E, int K, int N, int KG, int NB, hipStream_t s, int perm_k = 0);
