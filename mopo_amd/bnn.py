@@ -7,7 +7,7 @@ Mirrors the reference surface used on the hot path:
   * ``BNN.load_params`` / ``.mat`` layout    mopo/models/bnn.py:276-281, 588-592
   * ``BNN.train(inputs, targets, ...)``      mopo/models/bnn.py:369-503 (+ validate :351-362)
   * ``num_nets``, ``num_elites``, ``_model_inds``, ``scaler.cached_mu/cached_sigma``
-The forward runs in the HIP kernel ``bnn_fwd_kernel`` (csrc/bnn.hip); training steps in
+The forward runs in the HIP kernel ``bnn_fwd_kernel`` (csrc/bnn_kernels.h); training steps in
 csrc/bnn_train.hip (the loop control and numpy's RNG stream stay here, in the reference's order).
 There is no CPU path.
 """

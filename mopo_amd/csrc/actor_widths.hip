@@ -1,11 +1,10 @@
 // The rollout actor at the kernel widths 64, 96, ..., 224 (actor.h actor_kernel_hidden: every policy width up
-// to 256 is zero-embedded into the next multiple of 32 by pack_actor).  The kernels are actor.hip's
-// templates (included with MOPO_ACTOR_TEMPLATES_ONLY); they are instantiated here, in a translation unit of their own, so that the two product kernels
+// to 256 is zero-embedded into the next multiple of 32 by pack_actor).  The kernels are actor_kernels.h's
+// templates; they are instantiated here, in a translation unit of their own, so that the two product kernels
 // of actor.hip (widths 32 and 256) keep the register allocation they were tuned and measured with.
 // f16x3 runs actor_f16_kernel at these widths whether or not another launch runs beside it (the ring form
 // actor_f16q_kernel is the 256-wide product kernel's only).
-#define MOPO_ACTOR_TEMPLATES_ONLY 1
-#include "actor.hip"
+#include "actor_kernels.h"
 
 namespace mopo {
 

@@ -1,12 +1,10 @@
 // The ensemble forward at 8 and 16 hidden blocks of 16 (H = 128 and 256, and every narrower logical width
 // that mopo_bnn_create rounds up to them: internal.h bnn_form_blocks), exact-f32 MFMA form.
 //
-// The kernels are bnn.hip's templates (included with MOPO_BNN_TEMPLATES_ONLY: nothing else of that file is
-// compiled here); they are instantiated here, in a translation unit of their own,
+// The kernels are bnn_kernels.h's templates; they are instantiated here, in a translation unit of their own,
 // so that the kernels of bnn.hip keep the register allocation they were tuned and measured with.  The 16-bit
 // forms of the same widths are in bnn_widths16.hip.
-#define MOPO_BNN_TEMPLATES_ONLY 1
-#include "bnn.hip"
+#include "bnn_kernels.h"
 
 namespace mopo {
 

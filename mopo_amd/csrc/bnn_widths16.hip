@@ -1,11 +1,10 @@
 // The 16-bit forms (bf16x6, f16x3) of the ensemble forward at 8 and 16 hidden blocks (bnn_widths.hip has the
-// fp32 ones and the reason for the separate translation units): the ring kernel of bnn.hip at NB2 = 8
+// fp32 ones and the reason for the separate translation units): the ring kernel of bnn_kernels.h at NB2 = 8
 // and 16, whole even block counts, so no half-depth last k-group and no packed remainder.
 //
 // bf16x6 at 16 blocks is the one shape with knobs of its own (BNN_RING_PF_X6_16, BNN_RING_MINB_X6_16): its
 // registers are capped for 2 workgroups per CU, not 3 -- at 3 it spilled at every prefetch depth.
-#define MOPO_BNN_TEMPLATES_ONLY 1
-#include "bnn.hip"
+#include "bnn_kernels.h"
 
 namespace mopo {
 

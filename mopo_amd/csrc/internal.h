@@ -88,6 +88,10 @@ inline int bnn_device_hidden(int hidden, int dtype, bool wide) {
   return hidden > lo ? hidden : lo;
 }
 
+static const char* const kWide16Msg =
+    "bnn: a wide model (obs_dim + act_dim > 32 or obs_dim > 23) runs in fp32 at every hidden size up to 256 and at "
+    "385..400, and in bf16x6 / f16x3 at every hidden size up to 208; bf16, bf16x3 and "
+    "other hidden sizes are not supported there";
 static const char* const kWidths16Msg =
     "bnn: hidden sizes 65..128 and 209..256 run in fp32, bf16x6 and f16x3 (a wide model -- obs_dim + act_dim > 32 or "
     "obs_dim > 23 -- in fp32, and up to 128 in bf16x6 / f16x3); bf16 and bf16x3 are not supported there";
@@ -145,7 +149,17 @@ int launch_bnn_fwd_widths(const Bnn* h, int mode, const FwdArgs& a, hipStream_t 
 int launch_bnn_fwd_widths16(const Bnn* h, int mode, const FwdArgs& a, hipStream_t s);
 // W[E][K][N] (TF layout) -> fragment-major (see BnnDev) on stream s
 // perm_k: the K side is an input width in slot_feat order (mlp_tile.h)
-int pack_frags(const float* src, float* dst, int E, int K, int N, int KG, int NB, hipStream_t s, int perm_k = 0);
+// perm_n: the N side likewise (1), or the fused head's head_col order (2)
+int pack_frags(const float* src, float* dst, int E, int K, int N, int KG, int NB, hipStream_t s, int perm_k = 0,
+               int perm_n = 0);
+// the other packers of mopo_bnn_set_params (bnn_pack.h): hidden biases [E][N] -> slot order [E][NP] times mul;
+// 16-bit fragments of P parts per k-group of 32 (scale: f16x3's per-member 2^k, else the bf16 split; mstride:
+// fragments per member in dst); the packed remainder k-group KG - 1 of a bf16x6 input (bnn_kpack)
+int pack_bias(const float* src, float* dst, int E, int N, int NP, float mul, hipStream_t s);
+int pack_frags16(const float* src, short* dst, int E, int K, int N, int KG, int NB, int perm_n, int P,
+                 const float* scale, int64_t mstride, hipStream_t s);
+int pack_frags_kpack(const float* src, short* dst, int E, int K, int N, int KG, int NB, int perm_n, int64_t mstride,
+                     hipStream_t s);
 
 // termination kinds (mopo/static)
 // nobs: next_obs[d] for d < O -- an array or any accessor callable with d

@@ -3,7 +3,7 @@
 Mirrors ``FakeEnv`` (mopo/models/fake_env.py:4-131): same constructor, same ``step`` signature
 and return ``(next_obs, penalized_rewards, terminals, info)`` with the same info keys.  The whole
 step (ensemble forward + residual + sampling + elite gather + penalty + termination) runs in
-``mopo_fakeenv_step`` (csrc/bnn.hip + csrc/fakeenv.hip).
+``mopo_fakeenv_step`` (csrc/bnn_kernels.h + csrc/fakeenv.hip).
 
 RNG: ``rng='numpy'`` (default) consumes numpy's global legacy stream exactly like the reference
 -- ``np.random.normal(size=(E, B, D))`` then ``model.random_inds(B)`` -- so results match the

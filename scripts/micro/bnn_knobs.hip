@@ -1,7 +1,9 @@
 // Cost attribution for the ensemble forward (rollout mode, halfcheetah shape E=7 H=200, B=50000):
-// the same kernel built with one part disabled (-DBNN_KNOB_* in bnn.hip/mlp_tile.h; timing only,
-// results are garbage).  Build: scripts/micro/build_bnn_knobs.sh
+// the same kernel built with one part disabled (-DBNN_KNOB_* in bnn_kernels.h/mlp_tile.h; timing only,
+// results are garbage).  Build: scripts/micro/build_bnn_knobs.sh (it adds the bnn_widths*.hip units, which
+// launch_bnn_fwd calls for the forms of 8 and 16 hidden blocks)
 #include "../../mopo_amd/csrc/bnn.hip"
+#include "../../mopo_amd/csrc/bnn_api.hip"
 #include <cstdio>
 #include <random>
 

@@ -1,4 +1,4 @@
-"""The bf16x6 ring kernel's packed remainder k-group (bnn.hip bnn_fwd_ring_kernel<KP>, mlp_tile.h kpack_slot).
+"""The bf16x6 ring kernel's packed remainder k-group (bnn_kernels.h bnn_fwd_ring_kernel<KP>, mlp_tile.h kpack_slot).
 
 At H = 197..200 the last 32-deep k-group of every hidden-width input holds 2 real values per lane; the kernel runs
 it as one slice of one packed fragment per output block (two MFMAs, the second half full) instead of three slices

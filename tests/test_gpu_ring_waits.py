@@ -1,4 +1,4 @@
-"""The LDS-ring ensemble kernel (bnn.hip bnn_fwd_ring_kernel) reads its weight fragments from LDS ahead of the
+"""The LDS-ring ensemble kernel (bnn_kernels.h bnn_fwd_ring_kernel) reads its weight fragments from LDS ahead of the
 MFMAs that consume them, under counted ``s_waitcnt lgkmcnt(N)`` while slice copies are in flight.  A fragment
 consumed ahead of its wait is wrong in a few tiles of a few launches, so besides parity against the f64 oracle
 at every ring shape (H = 32, 64, 200: 2, 4 and 14 hidden blocks, the last with the half-K final k-group; both
