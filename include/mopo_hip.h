@@ -224,6 +224,11 @@ int mopo_bnn_train_logs(mopo_bnn_train_t h, float* h_logs, int n);
  * followed by the 8 list lengths into out (8 per + 8 ints; out may be NULL) and returns per (< 0: error).
  * No reference counterpart: a layout detail of bnn.py:425-432's minibatch op on this device. */
 int mopo_bnn_train_tile_lists(int E, int obs_dim, int act_dim, int hidden, int32_t* out, int64_t cap);
+/* Host only (no device call): the path a trainer of these dimensions steps on in this process.  Returns 1
+ * where mopo_bnn_train_epoch runs the fused row kernels and writes their 16-wide block counts G0 (inputs),
+ * GH (hidden), GD (both heads) to blocks3 (may be NULL); 0 for the generic grouped-GEMM path, which also
+ * serves every width when MOPO_TRAIN_ROWS=0 is set.  The trainer's own dispatch asks the same function. */
+int mopo_bnn_train_step_form(int obs_dim, int act_dim, int hidden, int* blocks3);
 /* Diagnostic builds only (MOPO_TRAIN_STAMPS=1; otherwise returns -1): the rows launch's
  * per-workgroup phase stamps of the last step, [block][8] (bnn_train.hip mopo_bnn_train_debug_stamps). */
 int mopo_bnn_train_debug_stamps(uint64_t* h_out, int64_t n);

@@ -88,6 +88,7 @@ SIGNATURES = {
     'mopo_bnn_train_restore': (c_int, [c_void_p, c_void_p]),
     'mopo_bnn_train_logs': (c_int, [c_void_p, c_void_p, c_int]),
     'mopo_bnn_train_tile_lists': (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_i64]),
+    'mopo_bnn_train_step_form': (c_int, [c_int, c_int, c_int, C.POINTER(c_int)]),
     'mopo_bnn_train_debug_stamps': (c_int, [c_void_p, c_i64]),
     'mopo_rollout_create': (c_int, [C.POINTER(c_void_p), c_void_p, c_i64, c_int]),
     'mopo_rollout_destroy': (c_int, [c_void_p]),

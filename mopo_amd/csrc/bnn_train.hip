@@ -418,7 +418,12 @@ int step_impl(Train* h, int par, int M, bool use_bstep, hipStream_t s) {
         g.push_back(dz);
       }
     }
-    if (launch_group(g, s, &ad, nullptr)) return -1;
+    // two problems per member: more than 8 members do not fit one group (gemm_group.h MAXP).  The problems are
+    // independent (Adam reads Pb[par] and writes the other buffer), so they may go in several launches.
+    for (size_t i = 0; i < g.size(); i += MAXP) {
+      const std::vector<GemmProb> part(g.begin() + i, g.begin() + std::min(i + (size_t)MAXP, g.size()));
+      if (launch_group(part, s, &ad, nullptr)) return -1;
+    }
   }
   return 0;
 }
@@ -438,17 +443,23 @@ int train_wgrad_tile() {
   return v == 16 ? 0 : 32;
 }
 
-bool use_rows(const Train* h) {
+// The dispatch rule's one home (pure, host only): does a step of these dimensions run the row kernels, and as
+// which train_rows_kernel<G0, GH, GD>?  use_rows and mopo_bnn_train_step_form both ask here; step_rows' lists
+// (MOPO_TRF / MOPO_TRR) must instantiate every form this admits.
+bool train_row_form(int IN, int H, int D, int* blocks3) {
   static const int env = [] {
     const char* e = std::getenv("MOPO_TRAIN_ROWS");
     return e ? std::atoi(e) : 1;
   }();
-  const Layout& L = h->L;
-  const int g0 = ceil_div(L.IN, 16), gh = ceil_div(L.H, 16), gd = ceil_div(2 * L.D, 16);
+  const int g0 = ceil_div(IN, 16), gh = ceil_div(H, 16), gd = ceil_div(2 * D, 16);
   const bool inst = ((gh == 13 || gh == 16 || gh == 8 || gh == 2) && ((g0 == 2 && gd == 3) || (g0 == 1 && gd == 2))) ||
                     ((gh == 13 || gh == 4) && g0 == 3 && gd == 4);   // step_rows' lists; the last: ant-sized rows
-  return env != 0 && inst && L.H % 4 == 0 && L.D % 2 == 0;
+  if (!(env != 0 && inst && H % 4 == 0 && D % 2 == 0)) return false;
+  if (blocks3) { blocks3[0] = g0; blocks3[1] = gh; blocks3[2] = gd; }
+  return true;
 }
+
+bool use_rows(const Train* h) { return train_row_form(h->L.IN, h->L.H, h->L.D, nullptr); }
 
 // the batch-level tail's inputs (train_rows.h train_loss_tail) -- the weight-gradient launch's block 0
 struct TrainTail {
@@ -1018,6 +1029,12 @@ static int tile_lists(int E, int obs_dim, int act_dim, int hidden, int order, in
     std::copy(host.begin(), host.end(), out);
   }
   return per;
+}
+
+// host only (no device call): which path a trainer of these dimensions steps on in this process
+extern "C" int mopo_bnn_train_step_form(int obs_dim, int act_dim, int hidden, int* blocks3) {
+  if (obs_dim < 1 || act_dim < 1 || hidden < 1) return 0;
+  return train_row_form(obs_dim + act_dim, hidden, obs_dim + 1, blocks3) ? 1 : 0;
 }
 
 // Diagnostic builds only (MOPO_TRAIN_STAMPS=1; otherwise -1): the rows launch's per-workgroup phase stamps

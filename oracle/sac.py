@@ -143,7 +143,8 @@ class Adam:
         self.b1p, self.b2p = b1, b2                                 # beta powers start at beta
 
     def apply(self, params, grads):
-        lr_t = self.lr * np.sqrt(1 - self.b2p) / (1 - self.b1p)
+        # a Python float: the same value in an fp64 run, and it leaves fp32 parameters and slots fp32
+        lr_t = float(self.lr * np.sqrt(1 - self.b2p) / (1 - self.b1p))
         for i, (p, g) in enumerate(zip(params, grads)):
             self.m[i] = self.m[i] + (g - self.m[i]) * (1 - self.b1)
             self.v[i] = self.v[i] + (g * g - self.v[i]) * (1 - self.b2)

@@ -10,6 +10,10 @@ Tolerances (fp32 device vs fp64 oracle on the same minibatch rows and scaler):
     2 lr: see assert_trained_close).
 Shapes: E=3, O=11, A=3, H=32 (one k-group) and the shipped E=7, O=17, A=6, H=200, batch 256 / 250.
 Integer work (shuffle_rows order, formatted rows) is bit-exact.
+
+The dispatch is covered in tests/test_gpu_train_forms.py (cases: tests/train_cases.py): every train_rows_kernel
+form, partial last hidden blocks, E = 1 .. 16, the generic path, MOPO_TRAIN_ROWS=0, the loss log, eval_mse
+sizes and member rows, snapshot / restore, each after asking mopo_bnn_train_step_form which path the shape took.
 """
 import ctypes as C
 
