@@ -324,6 +324,50 @@ typedef struct {
  * rollout_random is refused.  The statistics are reduced in a fixed order: bit-reproducible. */
 int mopo_rollout_evaluate(mopo_rollout_t h, const mopo_rollout_args* a, const mopo_eval_args* e, void* stream);
 
+/* ---- open-loop model validation on dataset trajectories ------------------------------------
+ * B segments of up to K steps: segment b starts at pool row r_b (d_start_idx, or the Philox draw of
+ * mopo_rollout_run over [0, size), size = pool->d_state[1] read on the device) with the f64 state obs[r_b];
+ * step k replays the DATASET's action actions[r_b + k] through one FakeEnv.step (fake_env.py:46-110) on the
+ * model's own predicted state and compares the prediction with the row's next_observations / rewards.  The
+ * policy is never run and the pool is only read.  No reference counterpart: the reference validates the
+ * model by its one-step holdout loss only (bnn.py:392-503).
+ * After step k (row j = r_b + k) the segment ends with reason 0 when k + 1 == K, else 1 when terminals[j] is
+ * set, else 3 when j + 1 >= size, else 2 when obs[j + 1] differs from next_obs[j] in any 32-bit pattern (an
+ * episode boundary without a flag: a timeout, or a wrapped pool's seam); otherwise it goes on.  A start row
+ * outside [0, size) (every row of an empty pool) ends at once: length 0, reason 3.  The termination rule's
+ * verdict on the predicted state does not end a segment; it is recorded in d_term_pred. */
+typedef struct {
+  /* outputs (device), any may be NULL; [K][B] arrays are indexed [step][segment], segment = row id -
+   * uid_offset, and hold NaN (d_term_pred, d_term_data: 0xFF) at steps k >= d_length[segment] */
+  double* d_err;            /* [K][B] sqrt(err_obs^2 + err_rew^2) */
+  double* d_err_obs;        /* [K][B] || predicted next state - next_obs[j] ||_2, f64 */
+  double* d_err_rew;        /* [K][B] predicted unpenalized reward - rewards[j] (signed) */
+  float* d_pen;             /* [K][B] the penalty u (fake_env.py:98-110), always computed */
+  uint8_t* d_term_pred;     /* [K][B] the termination rule on the predicted next state */
+  uint8_t* d_term_data;     /* [K][B] terminals[j] != 0 */
+  int32_t* d_length;        /* [B] steps taken */
+  uint8_t* d_end;           /* [B] end reason 0..3 */
+  int64_t* d_start;         /* [B] the start row r_b (-1: outside the pool) */
+  int64_t* d_steps;         /* [K] live segments per step */
+  double* d_stats;          /* [K + 1][16]; row k < K over the segments alive at step k, row K pooled over every
+                               live (step, segment) pair: 0 n, 1 mean err, 2 population std err, 3 max err,
+                               4 mean err_obs, 5 mean |err_rew|, 6 mean u, 7 population std u, 8 Pearson correlation
+                               of u with e* (err with penalty_learned_var, else err_obs; 0 when n < 2 or a variance
+                               is 0), 9 fraction u >= e*, 10 fraction d_term_pred != d_term_data, 11-15 zero; a row
+                               with n = 0 is all zero */
+} mopo_val_args;
+
+/* `a` as for mopo_rollout_run; used: B, horizon = K in [1, 4095], term_kind, penalty_learned_var,
+ * deterministic, the elites, seed / epoch / uid_offset and the parity streams d_start_idx, d_eps_obs,
+ * d_model_inds ([step][B] by the current compacted row, as mopo_rollout_evaluate).  d_pi_params, d_env_obs,
+ * env_size, penalty_coeff, rollout_random, d_steps and the actor fields are ignored.  Philox keys and
+ * counters are mopo_rollout_run's (start rows at step key epoch * 4096, step k at epoch * 4096 + 1 + k).
+ * Every 32 steps (environment MOPO_EVAL_POLL, 0: never) the live count is read back and the loop stops once
+ * no segment is alive; the results do not depend on it.  The statistics are reduced in a fixed order:
+ * bit-reproducible. */
+int mopo_rollout_validate(mopo_rollout_t h, const mopo_rollout_args* a, const mopo_pool_desc* pool,
+                          const mopo_val_args* v, void* stream);
+
 /* ---- SAC update (MOPO._do_training + _update_target) ------------------------------------
  * h_params: initial flat parameters (mopo_sac_param_count floats, layout above); target = copy
  * (target_init, mopo.py:449-450); log_alpha initial value (mopo.py:357-360); Adam lr / gamma / tau /

@@ -13,7 +13,9 @@ Offline additions: ``--data`` (local qlearning_dataset .npz: d4rl downloads are 
 or ``$D4RL_DATASET_DIR/<task>.npz`` named after the config's ``pool_load_path`` -- ``--model-dir``
 (``<model_name>.mat``, bnn.py:276-281), ``--epochs`` and ``--ensemble-dtype`` / ``--actor-dtype``
 (the forward arithmetic; default f16x3, held to the fp32 parity tolerances) and ``--model-eval-episodes`` /
-``--model-eval-length`` (episodes of the policy inside the learned model after every epoch; off by default).
+``--model-eval-length`` (episodes of the policy inside the learned model after every epoch; off by default),
+``--model-val-segments`` / ``--model-val-horizon`` (open-loop validation of the trained model on the dataset's
+own trajectories; off by default).
 ``--config`` is any
 importable module holding a ``params`` dict (examples/development/__init__.py:19-22), or one of the
 restated D4RL config names when the reference's ``examples`` package is not installed.
@@ -44,6 +46,8 @@ def get_parser():
     p.add_argument('--actor-dtype', default=None, choices=('fp32', 'bf16x6', 'f16x3'))
     p.add_argument('--model-eval-episodes', type=int, default=None)
     p.add_argument('--model-eval-length', type=int, default=None)
+    p.add_argument('--model-val-segments', type=int, default=None)
+    p.add_argument('--model-val-horizon', type=int, default=None)
     for f in ('--cpus', '--gpus', '--trial-cpus', '--trial-extra-cpus', '--max-failures'):
         p.add_argument(f, type=int, default=None)
     for f in ('--trial-gpus', '--trial-extra-gpus'):
@@ -72,7 +76,8 @@ def variant_spec(args):
     from .config import get_params
     params = get_params(args.config)
     kw = params['kwargs']
-    for k in ('ensemble_dtype', 'actor_dtype', 'model_eval_episodes', 'model_eval_length'):
+    for k in ('ensemble_dtype', 'actor_dtype', 'model_eval_episodes', 'model_eval_length', 'model_val_segments',
+              'model_val_horizon'):
         if getattr(args, k) is not None:
             kw[k] = getattr(args, k)
     kw.setdefault('ensemble_dtype', default_ensemble_dtype(kw.get('hidden_dim', 200)))
@@ -105,7 +110,8 @@ def main(argv=None):
             rargv += ['--model-dir', args.model_dir]
         if args.epochs is not None:
             rargv += ['--epochs', str(args.epochs)]
-        for k in ('ensemble_dtype', 'actor_dtype', 'model_eval_episodes', 'model_eval_length'):
+        for k in ('ensemble_dtype', 'actor_dtype', 'model_eval_episodes', 'model_eval_length', 'model_val_segments',
+              'model_val_horizon'):
             if getattr(args, k) is not None:
                 rargv += ['--' + k.replace('_', '-'), str(getattr(args, k))]
         run.main(rargv)

@@ -44,6 +44,12 @@ class EvalArgs(C.Structure):
                 ('d_pen_sum', c_void_p), ('d_length', c_void_p), ('d_terminated', c_void_p), ('d_stats', c_void_p)]
 
 
+class ValArgs(C.Structure):
+    _fields_ = [('d_err', c_void_p), ('d_err_obs', c_void_p), ('d_err_rew', c_void_p), ('d_pen', c_void_p),
+                ('d_term_pred', c_void_p), ('d_term_data', c_void_p), ('d_length', c_void_p), ('d_end', c_void_p), ('d_start', c_void_p),
+                ('d_steps', c_void_p), ('d_stats', c_void_p)]
+
+
 # name -> (restype, argtypes); every symbol declared in include/mopo_hip.h
 SIGNATURES = {
     'mopo_last_error': (C.c_char_p, []),
@@ -95,6 +101,8 @@ SIGNATURES = {
     'mopo_rollout_run': (c_int, [c_void_p, C.POINTER(RolloutArgs), C.POINTER(PoolDesc), c_void_p]),
     'mopo_rollout_run_staged': (c_int, [c_void_p, C.POINTER(RolloutArgs), C.POINTER(PoolDesc), c_void_p]),
     'mopo_rollout_evaluate': (c_int, [c_void_p, C.POINTER(RolloutArgs), C.POINTER(EvalArgs), c_void_p]),
+    'mopo_rollout_validate': (c_int, [c_void_p, C.POINTER(RolloutArgs), C.POINTER(PoolDesc), C.POINTER(ValArgs),
+                                      c_void_p]),
     'mopo_rollout_profile': (c_int, [c_void_p, c_int]),
     'mopo_rollout_profile_read': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     'mopo_sac_create': (c_int, [C.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_void_p, c_float,

@@ -1,5 +1,6 @@
-// The rollout handle and the pieces of rollout.hip that rollout_eval.hip (model-based policy evaluation)
-// launches as they are: the start-state gather, the wide models' scaled input rows and the compaction.
+// The rollout handle and the pieces of rollout.hip that rollout_eval.hip (model-based policy evaluation) and
+// rollout_val.hip (open-loop validation on dataset trajectories) launch as they are: the start-state gather,
+// the wide models' scaled input rows and the compaction.
 #pragma once
 #include "actor.h"
 
@@ -42,6 +43,13 @@ struct Rollout {
   void* eval_mem = nullptr;
   double* ev_ret; double* ev_pen_ret; double* ev_pen_sum;
   int32_t* ev_len; uint8_t* ev_term; float* ev_eps0; double* ev_stats;
+  // open-loop validation (rollout_val.hip), allocated on first use: the segments' start rows [Bmax] (as
+  // drawn, and clamped into the pool for the start gather), and the [K][B] tables / statistics a caller
+  // left NULL (val_tab, grown to the largest K * B asked for)
+  void* val_mem = nullptr;
+  int64_t* val_start; int64_t* val_gidx;
+  void* val_tab = nullptr;
+  size_t val_tab_bytes = 0;
 };
 
 constexpr int PB = 256;  // rows per block in post / compact
@@ -83,5 +91,7 @@ __global__ void rollout_xs_wide_kernel(const double* __restrict__ obs, const flo
 __global__ void rollout_compact_kernel(int O, const int* blockcnt, const uint8_t* keepf, const int* cnt,
                                        const double* obs_src, double* obs_dst, const int64_t* uid_src,
                                        int64_t* uid_dst, int* survivors);
+// defined in rollout_eval.hip
+__global__ void rollout_eval_advance_kernel(int* cnt, int64_t* steps, int i);
 
 }  // namespace mopo

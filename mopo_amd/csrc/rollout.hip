@@ -609,6 +609,8 @@ extern "C" int mopo_rollout_destroy(mopo_rollout_t hh) {
   if (h->wpk) (void)hipFree(h->wpk);
   if (h->mean_all) (void)hipFree(h->mean_all);
   if (h->eval_mem) (void)hipFree(h->eval_mem);
+  if (h->val_mem) (void)hipFree(h->val_mem);
+  if (h->val_tab) (void)hipFree(h->val_tab);
   delete h;
   return 0;
 }

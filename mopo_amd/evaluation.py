@@ -129,3 +129,95 @@ def model_evaluation_metrics_numpy(returns, lengths, penalized_returns, penalty_
             np.mean(np.asarray(penalized_returns, np.float64)), np.sum(np.asarray(penalty_sums, np.float64)) / np.sum(n),
             np.mean(np.asarray(terminated, np.float64)))
     return OrderedDict((k, float(v)) for k, v in zip(MODEL_EVAL_KEYS, vals))
+
+
+# ---- open-loop validation of the learned model on dataset trajectories (ModelRollout.validate,
+# csrc/rollout_val.hip) ----------------------------------------------------------------------------------
+# The dataset's own actions replayed through the model from dataset states, the model fed its predictions:
+# error(k) is the compounding-error curve, and the penalty recorded beside it shows whether u(s, a) tracks
+# (and bounds) the true error, the assumption MOPO's guarantee rests on.
+OPEN_LOOP_SLOTS = ('n', 'error', 'error-std', 'error-max', 'obs-error', 'reward-error', 'penalty', 'penalty-std',
+                   'penalty-error-corr', 'covered', 'termination-mismatch')
+END_REASONS = ('horizon', 'terminal', 'discontinuity', 'end-of-pool')
+
+
+def open_loop_metrics(stats):
+    """The device statistics ``ModelRollout.validate(...)['stats']`` (f64[K + 1, 16], columns in
+    ``OPEN_LOOP_SLOTS`` order; row k - 1 over the segments alive at step k, row K pooled over all steps) as an
+    OrderedDict: per step k = 1..K ``open_loop/error-h{k}`` (mean L2 error of the predicted (reward, next state)
+    after k model steps), ``obs-error-h{k}``, ``penalty-h{k}``, ``covered-h{k}`` (fraction with penalty >= error)
+    and ``alive-h{k}`` (segments that reached the step); pooled ``open_loop/error``, ``penalty``,
+    ``penalty-error-corr`` (Pearson), ``covered`` and ``termination-mismatch`` (the termination rule on the
+    predicted state against the data's flag)."""
+    s = stats.detach().cpu().numpy() if hasattr(stats, 'detach') else np.asarray(stats)
+    K = s.shape[0] - 1
+    out = OrderedDict()
+    for k in range(1, K + 1):
+        for name, col in (('error', 1), ('obs-error', 4), ('penalty', 6), ('covered', 9), ('alive', 0)):
+            out['open_loop/%s-h%d' % (name, k)] = float(s[k - 1, col])
+    for name, col in (('error', 1), ('penalty', 6), ('penalty-error-corr', 8), ('covered', 9),
+                      ('termination-mismatch', 10)):
+        out['open_loop/' + name] = float(s[K, col])
+    return out
+
+
+def open_loop_metrics_numpy(errors, obs_errors, reward_errors, penalties, term_pred, term_data, lengths,
+                            penalty_learned_var=True):
+    """The same [K + 1, 16] table from the per-segment host arrays ([K, B]; ``lengths`` [B]): what the device
+    reduction must equal.  Entry (k, b) counts when k < lengths[b]; the penalty is compared with ``errors`` for
+    the learned-variance penalty (a norm over all outputs) and with ``obs_errors`` for the mean-distance one (a
+    norm over the obs dims).  The correlation is 0 for fewer than two entries or a zero variance; a row
+    without entries is all zero."""
+    e, eo = np.asarray(errors, np.float64), np.asarray(obs_errors, np.float64)
+    er, u = np.asarray(reward_errors, np.float64), np.asarray(penalties, np.float64)
+    tp, td = np.asarray(term_pred), np.asarray(term_data)
+    K, B = e.shape
+    live = np.arange(K)[:, None] < np.asarray(lengths).reshape(1, B)
+    es = e if penalty_learned_var else eo
+    table = np.zeros((K + 1, 16))
+    for k in range(K + 1):
+        m = live[k] if k < K else live          # row K: k-major, then b -- the boolean mask's own order
+        sel = (lambda x: x[k][m]) if k < K else (lambda x: x[m])
+        n = int(m.sum())
+        if n == 0:
+            continue
+        ek, uk, sk = sel(e), sel(u), sel(es)
+        du, ds = uk - uk.mean(), sk - sk.mean()
+        vu, vs = float(np.sum(du * du)), float(np.sum(ds * ds))
+        corr = 0.0 if n < 2 or vu == 0.0 or vs == 0.0 else float(np.sum(du * ds)) / np.sqrt(vu * vs)
+        table[k, :11] = (n, ek.mean(), ek.std(), ek.max(), sel(eo).mean(), np.abs(sel(er)).mean(), uk.mean(),
+                         uk.std(), corr, np.mean(uk >= sk), np.mean(sel(tp) != sel(td)))
+    return table
+
+
+def segment_lengths_numpy(obs, next_obs, terminals, size, start, K):
+    """The continuation rule of the open-loop validation on the host: for each start row, ``(lengths,
+    end_reasons)`` of a segment of at most K steps over pool rows [0, size).  After step k (row j = start + k):
+    reason 0 (``END_REASONS``) when k + 1 == K, else 1 when ``terminals[j]``, else 3 when j + 1 >= size, else 2
+    when ``obs[j + 1]`` differs from ``next_obs[j]`` in any 32-bit pattern (a timeout boundary of a D4RL
+    qlearning_dataset, or a wrapped pool's seam; NaN cannot fool it), else the segment goes on.  A start outside
+    [0, size) takes no step: length 0, reason 3."""
+    o = np.ascontiguousarray(obs, np.float32).view(np.uint32)
+    no = np.ascontiguousarray(next_obs, np.float32).view(np.uint32)
+    t = np.asarray(terminals).reshape(-1) != 0
+    start = np.asarray(start, np.int64).reshape(-1)
+    lengths, ends = np.zeros(start.size, np.int32), np.zeros(start.size, np.uint8)
+    for b, r in enumerate(start):
+        if r < 0 or r >= size:
+            ends[b] = 3
+            continue
+        for k in range(K):
+            j = int(r) + k
+            lengths[b] = k + 1
+            if k + 1 == K:
+                ends[b] = 0
+            elif t[j]:
+                ends[b] = 1
+            elif j + 1 >= size:
+                ends[b] = 3
+            elif np.any(o[j + 1] != no[j]):
+                ends[b] = 2
+            else:
+                continue
+            break
+    return lengths, ends

@@ -37,7 +37,7 @@ class MOPO:
                  n_epochs=1000, n_train_repeat=1, batch_size=256, seed=88, reparameterize=True, max_model_t=None,
                  rollout_random=False, evaluation_environment=None, eval_n_episodes=10, eval_deterministic=True,
                  max_path_length=1000, ensemble_dtype=None, actor_dtype=None, model_eval_episodes=0,
-                 model_eval_length=None, **kwargs):
+                 model_eval_length=None, model_val_segments=0, model_val_horizon=None, **kwargs):
         """``ensemble_dtype``: the ensemble forward's arithmetic (``mopo_amd.bnn.DTYPES``), default
         ``DEFAULT_ENSEMBLE_DTYPE`` ('bf16x6': the f32 operands split exactly into 3 bf16 parts, 6 bf16
         MFMA products, f32 accumulate; 'fp32' above H = 256: ``bnn.default_ensemble_dtype``); 'fp32' runs
@@ -45,7 +45,10 @@ class MOPO:
         'bf16x6' / 'f16x3'; default the ensemble's for fp32 and bf16x6, else f16x3:
         ``rollout.default_actor_dtype``).  ``model_eval_episodes`` > 0: every epoch ends with that many
         episodes of at most ``model_eval_length`` (default ``max_path_length``) steps of the policy inside the
-        learned model (``_evaluate_in_model``: ``model_eval/*`` diagnostics); 0, the default, runs none."""
+        learned model (``_evaluate_in_model``: ``model_eval/*`` diagnostics); 0, the default, runs none.
+        ``model_val_segments`` > 0: right after the ensemble is trained, that many segments of at most
+        ``model_val_horizon`` (default ``rollout_length``) dataset steps are replayed open-loop through it
+        (``_validate_model``: ``model/open_loop/*`` diagnostics on every epoch's line); 0, the default, runs none."""
         if kwargs.get('action_prior', 'uniform') != 'uniform':   # mopo.py:364 asserts the uniform prior
             raise AssertionError("MOPO's policy loss supports action_prior='uniform' only (mopo.py:364)")
         self._pool = pool                                   # device SimpleReplayPool of env data
@@ -95,6 +98,8 @@ class MOPO:
         self._model_eval_episodes = int(model_eval_episodes)
         self._model_eval_length = int(max_path_length if model_eval_length is None else model_eval_length)
         self._eval_rollout = None
+        self._model_val_segments = int(model_val_segments)
+        self._model_val_horizon = int(rollout_length if model_val_horizon is None else model_val_horizon)
 
     # -- mopo.py:675-687
     def _set_rollout_length(self):
@@ -262,6 +267,27 @@ class MOPO:
                                           deterministic=self._deterministic)
         return model_evaluation_metrics(out['stats'])
 
+    # Philox key of the open-loop validation: bit 62 set as MODEL_EVAL_SEED_XOR's is (never a training key),
+    # and another constant, so the two diagnostics never share a draw either.
+    MODEL_VAL_SEED_XOR = 0x6F70656E6C6F6F70
+
+    def _validate_model(self):
+        """``model_val_segments`` segments of at most ``model_val_horizon`` steps of the env pool's own actions
+        replayed through the trained ensemble open-loop (``ModelRollout.validate``; the mean over all members,
+        the run's penalty kind): how fast the model's error compounds, and whether the penalty tracks it.  The
+        env pool's rows are mostly the model's own training rows, so the curve is in-distribution and
+        optimistic.  Reads the env pool and the model only: the pools, the SAC state, numpy's stream and the
+        training rollouts' Philox keys are left as they are."""
+        if self._model_val_segments <= 0:
+            return {}
+        from .evaluation import open_loop_metrics
+        n = self._model_val_segments
+        ro = ModelRollout(self._model, n, 1)
+        out = ro.validate(self._pool, n, self._model_val_horizon, self.fake_env.term_kind, self._model._model_inds,
+                          seed=self._seed ^ self.MODEL_VAL_SEED_XOR, epoch=0,
+                          penalty_learned_var=self.fake_env.penalty_learned_var, deterministic=True)
+        return open_loop_metrics(out['stats'])
+
     def train(self, n_epochs=None):
         """Generator of per-epoch diagnostics (mopo.py:650-651)."""
         if self._model_train_metrics is None:                                            # mopo.py:526-531
@@ -270,6 +296,7 @@ class MOPO:
             if self._rank == 0:   # multi-GPU: rank 0 trains, the others receive its packed weights below
                 self._model_train_metrics = self._train_model(batch_size=256, max_epochs=max_epochs,
                                                               holdout_ratio=0.2, max_t=self._max_model_t)
+                self._model_train_metrics.update(self._validate_model())
             if self._world > 1:
                 from .distributed import broadcast_model, broadcast_numpy_rng, broadcast_metrics, wait_for_src
                 wait_for_src(self._wait_group)   # no RCCL collective is pending while rank 0 trains

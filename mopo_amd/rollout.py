@@ -217,3 +217,53 @@ class ModelRollout:
         L.check(L.lib().mopo_rollout_evaluate(self._h, args, ev, L.stream_ptr(stream)))
         self._keepalive = keep
         return out
+
+    def validate(self, pool, n_segments, horizon, term_kind, elites, seed=0, epoch=0, start_idx=None, eps_obs=None,
+                 model_inds=None, uid_offset=0, stream=None, penalty_learned_var=True, deterministic=True):
+        """Open-loop model validation (csrc/rollout_val.hip): ``n_segments`` segments of at most ``horizon`` <=
+        4095 steps, each from a row of ``pool`` (a ``SimpleReplayPool`` or a ``PoolDesc``), replaying the
+        DATASET's actions through the model on the model's own predicted states and comparing every step with
+        the row's ``next_observations`` / ``rewards``.  A segment stops with the data: at a terminal flag (end
+        reason 1), where ``observations[j + 1]`` is not bit for bit ``next_observations[j]`` (2: an episode
+        boundary without a flag), at the pool's last valid row (3), or after ``horizon`` steps (0).  The policy
+        is never run, the pool is only read and numpy's global stream is not drawn from.  ``deterministic``
+        (the default here): the mean over all members, no sampling.  Returns device tensors: ``errors``,
+        ``obs_errors``, ``reward_errors`` (f64[horizon, n]; NaN past a segment's length), ``penalties``
+        (f32[horizon, n]), ``term_pred`` / ``term_data`` (u8[horizon, n]; 0xFF past the length), ``lengths``
+        (i32[n]), ``end_reasons`` (u8[n]), ``start_rows`` (int64[n]), ``steps`` (int64[horizon] live segments per step) and ``stats``
+        (f64[horizon + 1, 16], see ``evaluation.open_loop_metrics``).  A pool holding the model's own training
+        rows gives an in-distribution, optimistic curve; pass unseen trajectories for a held-out one."""
+        import torch
+        desc = pool.desc() if not isinstance(pool, L.PoolDesc) else pool
+        dev = pool._state.device if hasattr(pool, '_state') else torch.device('cuda')
+        n, K = int(n_segments), int(horizon)
+        kk = max(K, 1)
+        f64 = dict(dtype=torch.float64, device=dev)
+        u8 = dict(dtype=torch.uint8, device=dev)
+        out = {'errors': torch.full((kk, n), float('nan'), **f64),
+               'obs_errors': torch.full((kk, n), float('nan'), **f64),
+               'reward_errors': torch.full((kk, n), float('nan'), **f64),
+               'penalties': torch.full((kk, n), float('nan'), dtype=torch.float32, device=dev),
+               'term_pred': torch.full((kk, n), 255, **u8),
+               'term_data': torch.full((kk, n), 255, **u8),
+               'lengths': torch.zeros(n, dtype=torch.int32, device=dev),
+               'end_reasons': torch.zeros(n, **u8),
+               'start_rows': torch.full((n,), -1, dtype=torch.int64, device=dev),
+               'steps': torch.zeros(kk, dtype=torch.int64, device=dev),
+               'stats': torch.zeros((kk + 1, 16), **f64)}
+        keep = list(out.values())
+        # the policy / env-obs / penalty_coeff fields are ignored by the entry point: any device tensor names the
+        # device for _args, and its pointers to it are dropped again below
+        args = self._args(keep, out['stats'], 0, n, K, term_kind, 0.0, elites, seed, epoch, 0, start_idx, None,
+                          eps_obs, model_inds, uid_offset, out['steps'], penalty_learned_var, deterministic, False,
+                          None, 'fp32')
+        args.d_env_obs, args.env_size, args.d_steps = None, 0, None
+        va = L.ValArgs(d_err=L.ptr(out['errors']), d_err_obs=L.ptr(out['obs_errors']),
+                       d_err_rew=L.ptr(out['reward_errors']), d_pen=L.ptr(out['penalties']),
+                       d_term_pred=L.ptr(out['term_pred']), d_term_data=L.ptr(out['term_data']),
+                       d_length=L.ptr(out['lengths']), d_end=L.ptr(out['end_reasons']),
+                       d_start=L.ptr(out['start_rows']), d_steps=L.ptr(out['steps']),
+                       d_stats=L.ptr(out['stats']))
+        L.check(L.lib().mopo_rollout_validate(self._h, args, desc, va, L.stream_ptr(stream)))
+        self._keepalive = keep
+        return out

@@ -9,6 +9,8 @@ is trained from its initial weights to early stopping first (mopo.py:526-531).
 ``--ensemble-dtype`` / ``--actor-dtype``: the forward arithmetic (mopo_amd.bnn.DTYPES).
 ``--model-eval-episodes`` / ``--model-eval-length``: evaluate the policy inside the learned model after every
 epoch (``model_eval/*``: the return under the model, not a D4RL score); off by default.
+``--model-val-segments`` / ``--model-val-horizon``: replay dataset trajectories open-loop through the trained
+model (``model/open_loop/*``: the compounding error and the penalty's calibration); off by default.
 """
 import argparse
 import json
@@ -33,6 +35,11 @@ def main(argv=None):
                         'default: the config kwarg model_eval_episodes, else 0 = none)')
     p.add_argument('--model-eval-length', type=int, default=None,
                    help='step cap of those episodes, <= 4095 (default: max_path_length)')
+    p.add_argument('--model-val-segments', type=int, default=None,
+                   help='dataset segments replayed open-loop through the trained model (model/open_loop/* keys; '
+                        'default: the config kwarg model_val_segments, else 0 = none)')
+    p.add_argument('--model-val-horizon', type=int, default=None,
+                   help='step cap of those segments, <= 4095 (default: rollout_length)')
     a = p.parse_args(argv)
     from .config import DIMS, get_params
     from .loader import restore_pool
@@ -45,7 +52,9 @@ def main(argv=None):
     restore_pool(pool, a.data)
     over = {k: v for k, v in (('ensemble_dtype', a.ensemble_dtype), ('actor_dtype', a.actor_dtype)) if v}
     over.update((k, v) for k, v in (('model_eval_episodes', a.model_eval_episodes),
-                                    ('model_eval_length', a.model_eval_length)) if v is not None)
+                                    ('model_eval_length', a.model_eval_length),
+                                    ('model_val_segments', a.model_val_segments),
+                                    ('model_val_horizon', a.model_val_horizon)) if v is not None)
     algo = from_config(params, pool, static_fns[params['domain']], model_load_dir=a.model_dir, seed=a.seed, **over)
     for diag in algo.train(a.epochs):
         print(json.dumps({k: float(v) for k, v in diag.items()}), flush=True)
