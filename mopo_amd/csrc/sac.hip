@@ -226,7 +226,10 @@ static int sac_step_impl(Sac* h, int par, const mopo_pool_desc* env, const mopo_
     f.hd.iter = h->iter; f.hd.seed = seed; f.hd.eps_out[0] = h->eps_s; f.hd.eps_out[1] = h->eps_n;
     f.hd.gen_eps = (eps_in_s ? 0 : 1) | (eps_in_n ? 0 : 2);   // the heads whose noise is not injected
     f.st = Stamps{h->stamps, 0};
-    if (h->fuse == 1) { f.sync_reset = h->sync; f.n_sync = SYNC_N * nrb; }   // this step's F2 -> B1 counters
+    // fuse == 1: this step's F2 -> B1 counters are zeroed ahead of F1 (a memset node under capture), all
+    // SYNC_N * nrb of them: F1's own reset covers one block's 256 threads, fewer than the 8 * 64 counters of
+    // batch 1024.  The timeout word behind them stays.
+    if (h->fuse == 1) MOPO_HIP(hipMemsetAsync(h->sync, 0, (size_t)SYNC_N * nrb * SYNC_STRIDE * sizeof(unsigned), s));
     f.sync = h->sync;
     if (h->fuse < 2) {
       if (h->wide) sac_launch_fwd_wide(false, f, s);
@@ -290,14 +293,16 @@ static int sac_step_impl(Sac* h, int par, const mopo_pool_desc* env, const mopo_
     pr.log_alpha = P + o.total; pr.Wm = P + o.pWm; pr.Wl = P + o.pWl;
     pr.h2p = h->h2[0]; pr.h1p = h->h1[0]; pr.W2p = P + o.pW2;
     pr.dhead = h->dhead; pr.dh2p = h->dh2p; pr.dh1p = h->dh1p; pr.prior = h->prior;
-    d.gather = prefetch ? 1 : 0;
-    if (prefetch) {
+    // one z = 0 block (H <= 64 and batch <= 16) is the step control alone: the prefetch is then its own
+    // launch after the weight gradients (below)
+    const bool gather_b1 = prefetch && ncq1 * nrb >= 2;
+    d.gather = gather_b1 ? 1 : 0;
+    if (gather_b1) {
       d.ga = gather_args(h, 1 - par, env, mod, seed, nullptr);
       d.ga.iter_add = 1;                       // the next step's batch (the counter advances in B2)
     }
     d.st = Stamps{h->stamps, h->fuse >= 2 ? 0 : h->fuse ? 1 : 2};
     d.sync = h->sync;
-    if (ncq1 * nrb < 2 && prefetch) return fail("sac: B1 needs at least one gather block");
     static_assert(B1_COLS == RB_COLS && B1_WAVES == 4, "the fused launches share the F1 / F2 grid");
     f2.st = Stamps{h->stamps, h->fuse >= 2 ? 0 : 1};
     if (h->fuse == 2) {
@@ -352,6 +357,9 @@ static int sac_step_impl(Sac* h, int par, const mopo_pool_desc* env, const mopo_
     hipLaunchKernelGGL(sac_wgrad_kernel, dim3(1 + tot), dim3(1024), 0, s, g);
     MOPO_HIP(hipGetLastError());
   }
+  // B1 had no gather block: the next step's batch from a launch of its own (the loss tail above has advanced
+  // the step counter already, so iter_add stays 0)
+  if (prefetch && ceil_div(H, B1_COLS) * nrb < 2) return launch_gather(h, 1 - par, env, mod, seed, nullptr, s);
   return 0;
 }
 

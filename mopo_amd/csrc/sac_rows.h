@@ -442,7 +442,8 @@ struct FwdArgsR {
   FwdHead hd;
   Stamps st;
   unsigned* sync;                    // fused F2 + B1: [nrb][2] counters (policy / target instances) + timeout
-  unsigned* sync_reset; int n_sync;  // F1: block (0, 0, 0) zeroes the step's counters
+  unsigned* sync_reset; int n_sync;  // F1: block (0, 0, 0) zeroes the first n_sync <= 256 counters; the host leaves
+                                     //   it NULL (sac.hip zeroes all 8 nrb <= 512 of them ahead of F1 instead)
 };
 
 // the head of row r, action j (8 lanes per row; every lane of the 8 calls both halves): the loads (issued

@@ -42,7 +42,10 @@ class SAC:
       ``hidden_sizes``, default 256 x 2); ``pool`` becomes the default env pool of ``_do_training``.
 
     Limits (refused at construction by ``mopo_sac_create``): ``obs_dim <= 31`` and ``act_dim <= 8``, so the
-    critics read up to 39 inputs (ant: 27 + 8); hidden widths up to 256; ``batch_size <= 1024``.
+    critics read up to 39 inputs (ant: 27 + 8); hidden widths up to 256 (the device runs multiples of 16,
+    any other width zero-padded); ``batch_size`` in [1, 1024]; ``int(batch_size * real_ratio)`` in
+    [0, batch_size].  Every combination inside these limits steps, in parity and in perf mode
+    (tests/sac_cases.py).
     """
 
     def __init__(self, obs_dim, act_dim=None, *args, **kwargs):

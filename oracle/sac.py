@@ -17,7 +17,9 @@ Parity: restatement-pinned; cross-checked against torch autograd in tests.
 import numpy as np
 
 LOG_STD_MAX, LOG_STD_MIN, EPS = 2.0, -20.0, 1e-8          # mopo.py:271-273
-LOG2PI = np.log(2 * np.pi)
+LOG2PI = float(np.log(2 * np.pi))                               # Python floats: an fp32 run stays fp32
+LOG2 = float(np.log(2))
+ENT0 = float(0.5 * np.log(2 * np.pi * np.e))
 
 def _hs(H):
     """hidden_sizes (mopo.py:275-280): an int H is [H, H]."""
@@ -72,7 +74,7 @@ def pi_forward(P, s, eps):
     u = mu + eps * std                                              # :306
     zz = (u - mu) / (std + EPS)
     logp = np.sum(-0.5 * (zz ** 2 + 2 * ls + LOG2PI), axis=-1)       # :282-284
-    logp = logp - np.sum(2 * (np.log(2) - u - softplus(-2 * u)), axis=-1)   # :292
+    logp = logp - np.sum(2 * (LOG2 - u - softplus(-2 * u)), axis=-1)   # :292
     a = np.tanh(u)
     cache = dict(s=s, z1=z1, h1=h1, z2=z2, h2=h2, mu=mu, ls_raw=ls_raw, ls=ls, std=std, u=u, zz=zz,
                  a=a, eps=eps)
@@ -155,10 +157,13 @@ class Adam:
 
 
 class SACState:
-    def __init__(self, params, log_alpha=0.0, lr=3e-4):
-        self.params = [np.array(p, np.float64) for p in params]
+    def __init__(self, params, log_alpha=0.0, lr=3e-4, dtype=np.float64):
+        """``dtype=np.float32`` runs every step in fp32 (tests/sac_cases.py: how far rounding alone moves a
+        case); the batch and the noise must then be fp32 too."""
+        self.dtype = np.dtype(dtype)
+        self.params = [np.array(p, dtype) for p in params]
         self.target = [p.copy() for p in self.params]               # target_init :449-450
-        self.log_alpha = np.array(log_alpha, np.float64)
+        self.log_alpha = np.array(log_alpha, dtype)
         P, Q1, Q2 = split(self.params)
         self.opt_pi, self.opt_q1, self.opt_q2 = Adam(P, lr), Adam(Q1, lr), Adam(Q2, lr)
         self.opt_a = Adam([self.log_alpha], lr)
@@ -166,7 +171,7 @@ class SACState:
 
 def prior_log_prob(a):
     """softlearning sac.py:285-289: MultivariateNormalDiag(0, 1).log_prob(actions), per row."""
-    return -0.5 * np.sum(a * a, axis=-1) - 0.5 * a.shape[-1] * np.log(2 * np.pi)
+    return -0.5 * np.sum(a * a, axis=-1) - 0.5 * a.shape[-1] * LOG2PI
 
 
 def sac_step(st, batch, eps_s, eps_s2, gamma=0.99, tau=5e-3, reward_scale=1.0, target_entropy=-3.0, grads_out=None,
@@ -177,7 +182,7 @@ def sac_step(st, batch, eps_s, eps_s2, gamma=0.99, tau=5e-3, reward_scale=1.0, t
     log-prob of the policy's action from the policy loss (MOPO's own graph asserts 'uniform',
     mopo.py:364)."""
     s, a, s2 = batch['observations'], batch['actions'], batch['next_observations']
-    r, d = batch['rewards'][:, 0], batch['terminals'][:, 0].astype(np.float64)
+    r, d = batch['rewards'][:, 0], batch['terminals'][:, 0].astype(st.dtype)
     n = s.shape[0]
     P, Q1, Q2 = split(st.params)
     T = split(st.target)
@@ -200,13 +205,13 @@ def sac_step(st, batch, eps_s, eps_s2, gamma=0.99, tau=5e-3, reward_scale=1.0, t
     g_q1, _ = q_backward(Q1, c1, (q1 - y) / n)
     g_q2, _ = q_backward(Q2, c2, (q2 - y) / n)
     sel1 = q1_pi <= q2_pi                                           # tf.minimum grad -> x where x<=y
-    _, dx1 = q_backward(Q1, c1p, np.where(sel1, -1.0 / n, 0.0), need_params=False)
-    _, dx2 = q_backward(Q2, c2p, np.where(sel1, 0.0, -1.0 / n), need_params=False)
+    _, dx1 = q_backward(Q1, c1p, np.where(sel1, -1.0 / n, 0.0).astype(st.dtype), need_params=False)
+    _, dx2 = q_backward(Q2, c2p, np.where(sel1, 0.0, -1.0 / n).astype(st.dtype), need_params=False)
     O = s.shape[1]
     da = dx1[:, O:] + dx2[:, O:]
     if action_prior == 'normal':
         da = da + a_pi / n                                          # d/da of -mean(log N(a; 0, I))
-    g_pi = pi_backward(P, cpi, np.full(n, alpha / n), da)
+    g_pi = pi_backward(P, cpi, np.full(n, alpha / n, st.dtype), da)
     g_alpha = -np.mean(logp_pi + target_entropy)                    # d/dlog_alpha of :437-438
     if grads_out is not None:
         grads_out.update(pi=g_pi, q1=g_q1, q2=g_q2, alpha=g_alpha)
@@ -219,7 +224,7 @@ def sac_step(st, batch, eps_s, eps_s2, gamma=0.99, tau=5e-3, reward_scale=1.0, t
     st.log_alpha = st.opt_a.apply([st.log_alpha], [np.array(g_alpha)])[0]
     st.params = list(P) + list(Q1) + list(Q2)
     st.target = [(1 - tau) * t + tau * p for t, p in zip(st.target, st.params)]   # :446-447
-    pi_entropy = np.sum(np.log(std + 1e-8) + 0.5 * np.log(2 * np.pi * np.e), axis=-1)  # :341
+    pi_entropy = np.sum(np.log(std + 1e-8) + ENT0, axis=-1)  # :341
     return {'sac_pi/pi_global_norm': pi_gnorm, 'sac_Q/q_global_norm': q_gnorm,
             'Q/q1_loss': q1_loss, 'sac_Q/q2_loss': q2_loss,
             'sac_Q/q1': np.mean(q1), 'sac_Q/q2': np.mean(q2), 'sac_pi/alpha': alpha,
