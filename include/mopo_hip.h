@@ -90,6 +90,19 @@ int mopo_bnn_packed_copy(mopo_bnn_t h, int to_handle, void* d_buf, int64_t nbyte
 enum { MOPO_TERM_NONE = 0, MOPO_TERM_HALFCHEETAH = 0, MOPO_TERM_WALKER2D = 1, MOPO_TERM_HOPPER = 2,
        MOPO_TERM_ANT = 3, MOPO_TERM_HUMANOID = 4, MOPO_TERM_KINDS = 5 };
 
+/* The reward penalty u(s, a) of r~ = r - penalty_coeff * u, carried by the `penalty_learned_var` field of
+ * mopo_fakeenv_args and mopo_rollout_args (0 and 1 are the reference's two, bit for bit as before the other
+ * kinds existed).  mu_e / sigma_e: member e's head mean before the residual add / its std; d = 0 the reward,
+ * d = 1..O the observations; all E members count.
+ *   MEAN_DISTANCE  max_e ||mean_e - mean over members|| over the obs dims (fake_env.py:98-108)
+ *   MAX_ALEATORIC  max_e ||sigma_e|| over all D dims (fake_env.py:110; every D4RL config)
+ *   MAX_PAIRWISE   max_{i<j} ||mu_i - mu_j|| over the obs dims; 0 when E = 1 (MOReL's discrepancy)
+ *   ENSEMBLE_STD   sqrt(sum_d (1/E) sum_e [sigma_e[d]^2 + (mu_e[d] - mubar[d])^2]) over all D dims: the std
+ *                  of the ensemble taken as a mixture, aleatoric plus epistemic
+ * Every entry point that reads the field refuses a value outside [0, MOPO_PENALTY_KINDS). */
+enum { MOPO_PENALTY_MEAN_DISTANCE = 0, MOPO_PENALTY_MAX_ALEATORIC = 1, MOPO_PENALTY_MAX_PAIRWISE = 2,
+       MOPO_PENALTY_ENSEMBLE_STD = 3, MOPO_PENALTY_KINDS = 4 };
+
 typedef struct {
   const void* d_obs;        /* [B, O], f64 if obs_f64 else f32 */
   int obs_f64;
@@ -100,7 +113,8 @@ typedef struct {
   const int64_t* d_model_inds; /* [B] member index per row (bnn.py:343); unused if deterministic */
   int deterministic;        /* fake_env.py:69-70,84-86 */
   float penalty_coeff;      /* fake_env.py:97,115 */
-  int penalty_learned_var;  /* 1: max_e ||std_e||  0: max_e ||mean_e - mean|| (fake_env.py:98-110) */
+  int penalty_learned_var;  /* the penalty kind, MOPO_PENALTY_* (1: max_e ||std_e||  0: max_e ||mean_e - mean||,
+                               fake_env.py:98-110; 2 max_pairwise, 3 ensemble_std) */
   int term_kind;            /* MOPO_TERM_* */
   /* outputs (device) */
   double* d_next_obs;       /* [B, O] f64; must not alias d_obs */
@@ -117,6 +131,14 @@ typedef struct {
 } mopo_fakeenv_args;
 
 int mopo_fakeenv_step(mopo_bnn_t h, const mopo_fakeenv_args* a, void* stream);
+
+/* The penalty kinds MOPO_PENALTY_MAX_PAIRWISE / MOPO_PENALTY_ENSEMBLE_STD alone, from member outputs in
+ * mopo_bnn_predict's layout: d_mean, d_var [E, B, D = obs_dim + 1] f32 (the means before the residual add)
+ * -> d_penalty [B] f32, the value mopo_fakeenv_step computes from its own forward.  obs_dim <= 31, E >= 1; the
+ * reference's two kinds are refused here (they are part of mopo_fakeenv_step's post kernel).  No reference
+ * counterpart. */
+int mopo_penalty_from_predictions(int kind, const float* d_mean, const float* d_var, int E, int obs_dim, int64_t B,
+                                  float* d_penalty, void* stream);
 
 /* ---- policy (actor) --------------------------------------------------------------------
  * SAC parameters are one flat f32 buffer in reference creation order (mopo.py:32-33, 298-324):
@@ -259,8 +281,10 @@ typedef struct {
   /* outputs */
   int64_t* d_steps;         /* [horizon] rows added per step (mopo.py:748) */
   /* FakeEnv / rollout modes (fake_env.py:37-131, mopo.py:734-738) */
-  int penalty_learned_var;  /* 1: max_e ||std_e|| over all D dims (every D4RL config, fake_env.py:110)
-                               0: max_e ||mean_e - mean over members|| over the obs dims (fake_env.py:98-108) */
+  int penalty_learned_var;  /* the penalty kind, MOPO_PENALTY_*:
+                               1: max_e ||std_e|| over all D dims (every D4RL config, fake_env.py:110)
+                               0: max_e ||mean_e - mean over members|| over the obs dims (fake_env.py:98-108)
+                               2: max_pairwise, 3: ensemble_std (computed when penalty_coeff != 0; validate: always) */
   int deterministic;        /* 1: no sampling; next state = mean over ALL members of the means (fake_env.py:69-70,
                                84-86); the selection streams are unused */
   int rollout_random;       /* 1: actions ~ U(-1, 1) instead of the policy's (mopo.py:736-738) */
@@ -281,7 +305,7 @@ int mopo_rollout_run_staged(mopo_rollout_t h, const mopo_rollout_args* a,
                             const mopo_pool_desc* staging, void* stream);
 
 /* Live kernel timing (hipEvents on the launch stream around every launch, per kernel class:
- * 0 start-gather, 1 actor, 2 ensemble forward, 3 FakeEnv post, 4 compaction, 5 pointer advance).
+ * 0 start-gather, 1 actor, 2 ensemble forward, 3 FakeEnv post, 4 compaction, 5 pointer advance, 6 the penalty kernel of kinds >= 2).
  * profile_read synchronises the recorded events, returns summed ms and launch counts for the
  * runs since the last read, and clears them. */
 /* Steps [step_begin, step_end) of one staged rollout (the first call starts at 0; later calls continue
@@ -352,7 +376,7 @@ typedef struct {
   double* d_stats;          /* [K + 1][16]; row k < K over the segments alive at step k, row K pooled over every
                                live (step, segment) pair: 0 n, 1 mean err, 2 population std err, 3 max err,
                                4 mean err_obs, 5 mean |err_rew|, 6 mean u, 7 population std u, 8 Pearson correlation
-                               of u with e* (err with penalty_learned_var, else err_obs; 0 when n < 2 or a variance
+                               of u with e* (err for the kinds over all D outputs, 1 and 3, else err_obs; 0 when n < 2 or a variance
                                is 0), 9 fraction u >= e*, 10 fraction d_term_pred != d_term_data, 11-15 zero; a row
                                with n = 0 is all zero */
 } mopo_val_args;

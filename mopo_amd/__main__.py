@@ -15,7 +15,8 @@ or ``$D4RL_DATASET_DIR/<task>.npz`` named after the config's ``pool_load_path`` 
 (the forward arithmetic; default f16x3, held to the fp32 parity tolerances) and ``--model-eval-episodes`` /
 ``--model-eval-length`` (episodes of the policy inside the learned model after every epoch; off by default),
 ``--model-val-segments`` / ``--model-val-horizon`` (open-loop validation of the trained model on the dataset's
-own trajectories; off by default).
+own trajectories; off by default) and ``--penalty-kind`` (the reward penalty, mopo_amd.fake_env.PENALTY_KINDS;
+default: the config's choice).
 ``--config`` is any
 importable module holding a ``params`` dict (examples/development/__init__.py:19-22), or one of the
 restated D4RL config names when the reference's ``examples`` package is not installed.
@@ -26,6 +27,7 @@ import os
 import sys
 
 from .bnn import DTYPES, default_ensemble_dtype
+from .fake_env import PENALTY_KINDS
 
 EXAMPLES = ('examples.development',)
 COMMANDS = ('run_local', 'run_example_dry', 'run_example_debug')
@@ -48,6 +50,7 @@ def get_parser():
     p.add_argument('--model-eval-length', type=int, default=None)
     p.add_argument('--model-val-segments', type=int, default=None)
     p.add_argument('--model-val-horizon', type=int, default=None)
+    p.add_argument('--penalty-kind', default=None, choices=PENALTY_KINDS)
     for f in ('--cpus', '--gpus', '--trial-cpus', '--trial-extra-cpus', '--max-failures'):
         p.add_argument(f, type=int, default=None)
     for f in ('--trial-gpus', '--trial-extra-gpus'):
@@ -77,9 +80,11 @@ def variant_spec(args):
     params = get_params(args.config)
     kw = params['kwargs']
     for k in ('ensemble_dtype', 'actor_dtype', 'model_eval_episodes', 'model_eval_length', 'model_val_segments',
-              'model_val_horizon'):
+              'model_val_horizon', 'penalty_kind'):
         if getattr(args, k) is not None:
             kw[k] = getattr(args, k)
+    from .config import resolve_penalty_kind
+    resolve_penalty_kind(kw)
     kw.setdefault('ensemble_dtype', default_ensemble_dtype(kw.get('hidden_dim', 200)))
     seeds = [args.seed + i for i in range(max(args.num_samples, 1))]
     return {'algorithm_params': params, 'run_params': {'seeds': seeds, 'checkpoint_frequency': args.checkpoint_frequency},
@@ -111,7 +116,7 @@ def main(argv=None):
         if args.epochs is not None:
             rargv += ['--epochs', str(args.epochs)]
         for k in ('ensemble_dtype', 'actor_dtype', 'model_eval_episodes', 'model_eval_length', 'model_val_segments',
-              'model_val_horizon'):
+              'model_val_horizon', 'penalty_kind'):
             if getattr(args, k) is not None:
                 rargv += ['--' + k.replace('_', '-'), str(getattr(args, k))]
         run.main(rargv)

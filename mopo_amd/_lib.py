@@ -63,6 +63,7 @@ SIGNATURES = {
     'mopo_bnn_packed_bytes': (c_i64, [c_void_p]),
     'mopo_bnn_packed_copy': (c_int, [c_void_p, c_int, c_void_p, c_i64, c_void_p]),
     'mopo_fakeenv_step': (c_int, [c_void_p, C.POINTER(FakeEnvArgs), c_void_p]),
+    'mopo_penalty_from_predictions': (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_i64, c_void_p, c_void_p]),
     'mopo_sac_param_count': (c_i64, [c_int, c_int, c_int]),
     'mopo_actor_forward': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_i64, c_void_p,
                                    c_u64, c_u32, c_void_p, c_void_p, c_void_p]),

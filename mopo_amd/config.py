@@ -85,6 +85,19 @@ def _restated(key):
     return p
 
 
+def resolve_penalty_kind(kwargs):
+    """The ``penalty_kind`` kwarg of a config (or ``--penalty-kind``): one of ``fake_env.PENALTY_KINDS``, or
+    absent / None for the reference's choice by ``penalty_learned_var``.  A named kind decides: the D4RL
+    configs' own ``penalty_learned_var: True`` (base_mopo.py) is restated to agree with it, so that naming a
+    kind on top of such a config is no contradiction.  In place; returns ``kwargs``."""
+    kind = kwargs.get('penalty_kind')
+    if kind is not None:
+        from .fake_env import PENALTY_KINDS, penalty_kind_id
+        kwargs['penalty_kind'] = PENALTY_KINDS[penalty_kind_id(kind)]
+        kwargs['penalty_learned_var'] = kwargs['penalty_kind'] == 'max_aleatoric'
+    return kwargs
+
+
 def load_module_params(name, params_name='params'):
     """examples/development/__init__.py:19-22: ``importlib.import_module(name).params``; None when
     the module itself does not exist (an import error raised INSIDE an existing module propagates)."""
@@ -113,6 +126,7 @@ def get_params(name):
         if k not in params:
             raise KeyError('config %r: params has no %r' % (name, k))
     p = deep_update(DEFAULTS, params, ADDITIONAL)
+    resolve_penalty_kind(p['kwargs'])   # a config's own 'penalty_kind' kwarg
     # softlearning/algorithms/utils.py:43-48: model_name = exp_name with '-' + '_smv' + '_1_0' (always set)
     p['kwargs']['model_name'] = (p['exp_name'].replace('_', '-') +
                                  ('_smv' if p['kwargs'].get('separate_mean_var') else '') + '_1_0')

@@ -75,6 +75,7 @@ extern "C" int mopo_bnn_destroy(mopo_bnn_t hh) {
   if (!h) return 0;
   if (h->buf) (void)hipFree(h->buf);
   if (h->bbuf) (void)hipFree(h->bbuf);
+  if (h->pen_buf) (void)hipFree(h->pen_buf);
   delete h;
   return 0;
 }

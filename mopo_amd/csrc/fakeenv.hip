@@ -6,6 +6,7 @@
 // dtype rules follow the reference: means stay f32 after the in-place residual add
 // (fake_env.py:66), the noisy sample is f64 (fake_env.py:72), penalty is an f32 norm.
 #include "internal.h"
+#include "penalty.h"
 
 namespace mopo {
 
@@ -13,7 +14,9 @@ constexpr int MAXD = 32;
 
 // Every per-row quantity is re-read from the (L1/L2-resident) inputs where it is used instead of being
 // held in per-thread arrays indexed by the runtime D: such arrays live in scratch (528 B per lane).
-__global__ __launch_bounds__(256) void fakeenv_post_kernel(const mopo_fakeenv_args a, int E, int O, int A) {
+// pen_ready: the row's penalty already computed (kinds >= 2, ensemble_penalty_kernel), else NULL
+__global__ __launch_bounds__(256) void fakeenv_post_kernel(const mopo_fakeenv_args a, int E, int O, int A,
+                                                           const float* __restrict__ pen_ready) {
   const int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (b >= a.B) return;
   const int D = O + 1;
@@ -81,7 +84,9 @@ __global__ __launch_bounds__(256) void fakeenv_post_kernel(const mopo_fakeenv_ar
   // penalty (fake_env.py:97-115)
   float pen = 0.f;
   if (a.penalty_coeff != 0.f) {
-    if (a.penalty_learned_var) {
+    if (pen_ready) {
+      pen = pen_ready[b];
+    } else if (a.penalty_learned_var) {
       for (int e = 0; e < E; ++e) {
         float s2 = 0.f;
         for (int d = 0; d < D; ++d) {
@@ -130,6 +135,8 @@ extern "C" int mopo_fakeenv_step(mopo_bnn_t hh, const mopo_fakeenv_args* a, void
   MOPO_REQUIRE(h->O + 1 <= MAXD, "mopo_fakeenv_step: obs_dim too large");
   MOPO_REQUIRE(a->B >= 0, "mopo_fakeenv_step: negative batch");
   MOPO_REQUIRE(a->term_kind >= 0 && a->term_kind < MOPO_TERM_KINDS, "mopo_fakeenv_step: unknown term_kind");
+  MOPO_REQUIRE(a->penalty_learned_var >= 0 && a->penalty_learned_var < MOPO_PENALTY_KINDS,
+               std::string("mopo_fakeenv_step") + kPenaltyKindMsg);
   if (a->B == 0) return 0;  // empty batch: nothing to read or write (empty buffers may be NULL)
   MOPO_REQUIRE(a->d_ens_mean && a->d_ens_var, "mopo_fakeenv_step: ensemble workspaces required");
   MOPO_REQUIRE(a->deterministic || (a->d_noise_sel && a->d_model_inds),
@@ -147,8 +154,26 @@ extern "C" int mopo_fakeenv_step(mopo_bnn_t hh, const mopo_fakeenv_args* a, void
   f.mean = a->d_ens_mean;
   f.var = a->d_ens_var;
   if (launch_bnn_fwd(h, FWD_PREDICT, f, s)) return -1;
+  const float* pen_ready = nullptr;
+  if (a->penalty_learned_var >= MOPO_PENALTY_MAX_PAIRWISE && a->penalty_coeff != 0.f) {
+    // the predict layout [E][B][D], variances; into the handle's [B] scratch (earlier steps of this handle
+    // ran on this stream: one handle = one stream at a time)
+    if (h->pen_rows < a->B) {
+      if (h->pen_buf) (void)hipFree(h->pen_buf);
+      h->pen_buf = nullptr;
+      h->pen_rows = 0;
+      MOPO_HIP(hipMalloc(&h->pen_buf, (size_t)a->B * sizeof(float)));
+      h->pen_rows = a->B;
+    }
+    PenaltyArgs pa{};
+    pa.mean = a->d_ens_mean; pa.spread = a->d_ens_var; pa.stride = a->B; pa.spread_is_var = 1;
+    pa.E = h->E; pa.O = h->O; pa.B = a->B; pa.kind = a->penalty_learned_var;
+    pa.pen = reinterpret_cast<uint32_t*>(h->pen_buf);
+    if (launch_ensemble_penalty(pa, s)) return -1;
+    pen_ready = h->pen_buf;
+  }
   hipLaunchKernelGGL(fakeenv_post_kernel, dim3(ceil_div((int)a->B, 256)), dim3(256), 0, s, *a, h->E, h->O,
-                     h->A);
+                     h->A, pen_ready);
   MOPO_HIP(hipGetLastError());
   return 0;
 }

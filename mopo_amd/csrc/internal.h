@@ -104,6 +104,9 @@ struct Bnn {
   uint16_t* bbuf = nullptr;  // bf16 packed weights
   int64_t buf_bytes = 0, bbuf_bytes = 0;  // sizes of buf / bbuf (mopo_bnn_packed_copy)
   BnnDev dev{};
+  // mopo_fakeenv_step, penalty kinds >= 2: the [pen_rows] ready penalties of penalty.hip, grown on demand
+  float* pen_buf = nullptr;
+  int64_t pen_rows = 0;
 };
 
 // Input view: features [0, O) from xa (row stride sa), [O, IN) from xb (row stride sb).

@@ -50,7 +50,15 @@ struct Rollout {
   int64_t* val_start; int64_t* val_gidx;
   void* val_tab = nullptr;
   size_t val_tab_bytes = 0;
+  // every member's std beside mean_all, same size, allocated on first use (penalty kinds >= 2, penalty.hip)
+  float* std_all = nullptr;
 };
+
+// Penalty kinds >= 2 (penalty.hip): allocates mean_all / std_all on first use.  Then, per step, the caller
+// sets FwdArgs::mean_all / std_all, launches the ensemble, rollout_penalty on the same stream (rows at element
+// offset `off` of the handle's buffers, live count *cnt) and the post kernel with pen_dist = 0.
+int rollout_penalty_alloc(Rollout* h);
+int rollout_penalty(Rollout* h, int kind, int64_t off, int64_t n, const int* cnt, hipStream_t s);
 
 constexpr int PB = 256;  // rows per block in post / compact
 

@@ -10,11 +10,12 @@
 //   rollout_compact   order-preserving non-terminal compaction  obs = next_obs[~term] (mopo.py:753-758)
 //   step_advance      steps_added / pool pointer & size (mopo.py:748; flexible_replay_pool.py:45-48)
 #include "mlp_tile.h"
+#include "penalty.h"
 #include "rollout.h"
 
 namespace mopo {
 
-enum { KC_START = 0, KC_ACTOR, KC_BNN, KC_POST, KC_COMPACT, KC_ADVANCE, KC_N };
+enum { KC_START = 0, KC_ACTOR, KC_BNN, KC_POST, KC_COMPACT, KC_ADVANCE, KC_PENALTY, KC_N };
 
 // scoped hipEvent pair on the launch stream (only when profiling is enabled)
 struct KTimer {
@@ -352,6 +353,8 @@ static int run_impl(Rollout* h, const mopo_rollout_args* a, const mopo_pool_desc
   MOPO_REQUIRE(a->B >= 0 && a->B <= h->Bmax, "rollout: B exceeds the handle's max_batch");
   MOPO_REQUIRE(a->horizon >= 0 && a->horizon <= h->Hmax, "rollout: horizon exceeds max_horizon");
   MOPO_REQUIRE(a->term_kind >= 0 && a->term_kind < MOPO_TERM_KINDS, "rollout: unknown term_kind");
+  MOPO_REQUIRE(a->penalty_learned_var >= 0 && a->penalty_learned_var < MOPO_PENALTY_KINDS,
+               std::string("rollout") + kPenaltyKindMsg);
   MOPO_REQUIRE(a->d_env_obs && a->env_size > 0, "rollout: empty env pool");
   MOPO_REQUIRE(a->d_pi_params, "rollout: NULL policy params");
   MOPO_REQUIRE(a->d_model_inds || (a->d_elites && a->n_elites > 0), "rollout: elites required");
@@ -407,9 +410,13 @@ static int run_impl(Rollout* h, const mopo_rollout_args* a, const mopo_pool_desc
   // every member's mean per row is needed by the mean-distance penalty and by deterministic steps
   const bool det = a->deterministic != 0;
   const bool pen_dist = a->penalty_learned_var == 0 && a->penalty_coeff != 0.f;
-  const bool need_all = det || pen_dist;
+  // kinds >= 2 (penalty.hip): every member's mean and std, reduced by one kernel behind the ensemble
+  const int pen_kind = a->penalty_learned_var >= MOPO_PENALTY_MAX_PAIRWISE && a->penalty_coeff != 0.f
+                           ? a->penalty_learned_var : 0;
+  const bool need_all = det || pen_dist || pen_kind;
   if (need_all && !h->mean_all)
     MOPO_HIP(hipMalloc(&h->mean_all, (size_t)bnn->E * h->Bmax * D * sizeof(float)));
+  if (pen_kind && rollout_penalty_alloc(h)) return -1;
   MOPO_REQUIRE(!a->rollout_random || a->d_act_uniform || !a->d_eps_act,
                "rollout: parity mode with rollout_random needs the injected uniforms (d_act_uniform)");
   int oc = h->oc, uc = h->uc;
@@ -453,10 +460,15 @@ static int run_impl(Rollout* h, const mopo_rollout_args* a, const mopo_pool_desc
     f.pen_bits = h->pen + off; f.sel = det ? nullptr : h->sel + off; f.mean_sel = h->mean_sel + off * D;
     f.std_sel = h->std_sel + off * D;
     f.mean_all = need_all ? h->mean_all + off * D : nullptr;
+    f.std_all = pen_kind ? h->std_all + off * D : nullptr;
     f.all_stride = h->Bmax;
     {
       KTimer t(h, KC_BNN, ss);
       if (launch_bnn_fwd(bnn, FWD_ROLLOUT, f, ss)) return -1;
+    }
+    if (pen_kind) {
+      KTimer t(h, KC_PENALTY, ss);
+      if (rollout_penalty(h, pen_kind, off, n, cnt, ss)) return -1;
     }
 
     PostArgs pa{};
@@ -608,6 +620,7 @@ extern "C" int mopo_rollout_destroy(mopo_rollout_t hh) {
   if (h->mem) (void)hipFree(h->mem);
   if (h->wpk) (void)hipFree(h->wpk);
   if (h->mean_all) (void)hipFree(h->mean_all);
+  if (h->std_all) (void)hipFree(h->std_all);
   if (h->eval_mem) (void)hipFree(h->eval_mem);
   if (h->val_mem) (void)hipFree(h->val_mem);
   if (h->val_tab) (void)hipFree(h->val_tab);

@@ -10,6 +10,7 @@
 //   rollout_compact          obs = next_obs[~term] (skipped for the never-done domains)
 //   rollout_eval_advance     live count <- survivors, steps[i] (with compaction only)
 // then rollout_eval_stats reduces the per-episode sums to evaluate_rollouts' statistics.
+#include "penalty.h"
 #include "rollout.h"
 
 #include <cstdlib>
@@ -211,6 +212,8 @@ extern "C" int mopo_rollout_evaluate(mopo_rollout_t hh, const mopo_rollout_args*
                "mopo_rollout_evaluate: the episode length T must be in [1, 4095] (the Philox step key is "
                "epoch * 4096 + 1 + step)");
   MOPO_REQUIRE(a->term_kind >= 0 && a->term_kind < MOPO_TERM_KINDS, "mopo_rollout_evaluate: unknown term_kind");
+  MOPO_REQUIRE(a->penalty_learned_var >= 0 && a->penalty_learned_var < MOPO_PENALTY_KINDS,
+               std::string("mopo_rollout_evaluate") + kPenaltyKindMsg);
   MOPO_REQUIRE(!(e->policy_deterministic && a->rollout_random),
                "mopo_rollout_evaluate: policy_deterministic with rollout_random (uniform actions have no mean)");
   MOPO_REQUIRE(a->d_env_obs && a->env_size > 0, "mopo_rollout_evaluate: empty env pool");
@@ -257,9 +260,13 @@ extern "C" int mopo_rollout_evaluate(mopo_rollout_t hh, const mopo_rollout_args*
   }
   const bool det = a->deterministic != 0;
   const bool pen_dist = a->penalty_learned_var == 0 && a->penalty_coeff != 0.f;
-  const bool need_all = det || pen_dist;
+  // kinds >= 2 (penalty.hip): every member's mean and std, reduced by one kernel behind the ensemble
+  const int pen_kind = a->penalty_learned_var >= MOPO_PENALTY_MAX_PAIRWISE && a->penalty_coeff != 0.f
+                           ? a->penalty_learned_var : 0;
+  const bool need_all = det || pen_dist || pen_kind;
   if (need_all && !h->mean_all)
     MOPO_HIP(hipMalloc(&h->mean_all, (size_t)bnn->E * h->Bmax * D * sizeof(float)));
+  if (pen_kind && rollout_penalty_alloc(h)) return -1;
 
   h->next_step = 0;   // a staged step range must not continue across an evaluation
   hipLaunchKernelGGL(rollout_eval_init_kernel, dim3(ceil_div((int)B, 256)), dim3(256), 0, s, B, ret, pen_ret,
@@ -307,8 +314,10 @@ extern "C" int mopo_rollout_evaluate(mopo_rollout_t hh, const mopo_rollout_args*
     f.B = B; f.d_count = h->cnt; f.xs = h->xs;
     f.pen_bits = h->pen; f.sel = det ? nullptr : h->sel; f.mean_sel = h->mean_sel; f.std_sel = h->std_sel;
     f.mean_all = need_all ? h->mean_all : nullptr;
+    f.std_all = pen_kind ? h->std_all : nullptr;
     f.all_stride = h->Bmax;
     if (launch_bnn_fwd(bnn, FWD_ROLLOUT, f, s)) return -1;
+    if (pen_kind && rollout_penalty(h, pen_kind, 0, B, h->cnt, s)) return -1;
 
     EvalPostArgs ea{};
     PostArgs& pa = ea.p;

@@ -15,6 +15,7 @@
 //   rollout_compact          obs = next_obs[continues]
 //   rollout_eval_advance     live count <- survivors
 // then rollout_val_stats reduces the [K][B] tables to the per-step and pooled statistics.
+#include "penalty.h"
 #include "rollout.h"
 
 #include <cstdlib>
@@ -241,8 +242,8 @@ __global__ __launch_bounds__(256) void rollout_val_post_kernel(const ValPostArgs
 // k < K over the segments alive at step k, thread t folding segments t, t + 256, ...; row K over every live
 // (step, segment) pair in step-major order, thread t folding pairs t, t + 256, ...; then a fixed binary
 // tree over the 256 partials, and a second pass around the means for the deviations -- the same bits every
-// run.  e* is err for the learned-variance penalty (a norm over all D outputs), err_obs for the
-// mean-distance penalty (a norm over the obs dims).
+// run.  e* is err for the penalty kinds that are norms over all D outputs (max_aleatoric, ensemble_std),
+// err_obs for the kinds over the obs dims (mean_distance, max_pairwise): pen_dist = "over the obs dims".
 constexpr int VST = 256;
 enum { VQ_N = 0, VQ_ERR, VQ_EOBS, VQ_EREW, VQ_PEN, VQ_COVER, VQ_MIS, VQ_MAX, VQ_COUNT };
 __global__ __launch_bounds__(VST) void rollout_val_stats_kernel(ValTabs t, int64_t B, int K, int pen_dist,
@@ -331,6 +332,8 @@ extern "C" int mopo_rollout_validate(mopo_rollout_t hh, const mopo_rollout_args*
                "mopo_rollout_validate: the segment length K must be in [1, 4095] (the Philox step key is "
                "epoch * 4096 + 1 + step)");
   MOPO_REQUIRE(a->term_kind >= 0 && a->term_kind < MOPO_TERM_KINDS, "mopo_rollout_validate: unknown term_kind");
+  MOPO_REQUIRE(a->penalty_learned_var >= 0 && a->penalty_learned_var < MOPO_PENALTY_KINDS,
+               std::string("mopo_rollout_validate") + kPenaltyKindMsg);
   MOPO_REQUIRE(a->deterministic || a->d_model_inds || (a->d_elites && a->n_elites > 0),
                "mopo_rollout_validate: elites required");
   MOPO_REQUIRE(pool->d_obs && pool->d_act && pool->d_rew && pool->d_term && pool->d_next_obs && pool->d_state &&
@@ -375,9 +378,14 @@ extern "C" int mopo_rollout_validate(mopo_rollout_t hh, const mopo_rollout_args*
 
   const bool det = a->deterministic != 0;
   const bool pen_dist = a->penalty_learned_var == 0;   // the penalty is always computed
-  const bool need_all = det || pen_dist;
+  // kinds >= 2 (penalty.hip): every member's mean and std, reduced by one kernel behind the ensemble
+  const int pen_kind = a->penalty_learned_var >= MOPO_PENALTY_MAX_PAIRWISE ? a->penalty_learned_var : 0;
+  // the error the penalty is compared with: err_obs for the kinds over the observation outputs (0 and 2)
+  const bool over_obs = pen_dist || pen_kind == MOPO_PENALTY_MAX_PAIRWISE;
+  const bool need_all = det || pen_dist || pen_kind;
   if (need_all && !h->mean_all)
     MOPO_HIP(hipMalloc(&h->mean_all, (size_t)bnn->E * h->Bmax * D * sizeof(float)));
+  if (pen_kind && rollout_penalty_alloc(h)) return -1;
 
   h->next_step = 0;   // a staged step range must not continue across a validation
   hipLaunchKernelGGL(rollout_val_init_kernel, dim3((unsigned)((kb + 255) / 256)), dim3(256), 0, s, B, K, t, *pool,
@@ -414,8 +422,10 @@ extern "C" int mopo_rollout_validate(mopo_rollout_t hh, const mopo_rollout_args*
     f.B = B; f.d_count = h->cnt; f.xs = wide ? h->xs : nullptr;
     f.pen_bits = h->pen; f.sel = det ? nullptr : h->sel; f.mean_sel = h->mean_sel; f.std_sel = h->std_sel;
     f.mean_all = need_all ? h->mean_all : nullptr;
+    f.std_all = pen_kind ? h->std_all : nullptr;
     f.all_stride = h->Bmax;
     if (launch_bnn_fwd(bnn, FWD_ROLLOUT, f, s)) return -1;
+    if (pen_kind && rollout_penalty(h, pen_kind, 0, B, h->cnt, s)) return -1;
 
     ValPostArgs va{};
     PostArgs& pa = va.p;
@@ -443,7 +453,7 @@ extern "C" int mopo_rollout_validate(mopo_rollout_t hh, const mopo_rollout_args*
       if (live == 0) break;
     }
   }
-  hipLaunchKernelGGL(rollout_val_stats_kernel, dim3(K + 1), dim3(VST), 0, s, t, B, K, pen_dist ? 1 : 0, stats,
+  hipLaunchKernelGGL(rollout_val_stats_kernel, dim3(K + 1), dim3(VST), 0, s, t, B, K, over_obs ? 1 : 0, stats,
                      v->d_steps);
   MOPO_HIP(hipGetLastError());
   return 0;

@@ -88,8 +88,8 @@ class DistributedRollout:
 
     def run(self, env_obs, pi_params, pool, term_kind, penalty_coeff, elites, seed=0, epoch=0, pi_hidden=256,
             **modes):
-        """``modes``: the FakeEnv / rollout modes of ModelRollout.run (penalty_learned_var, deterministic,
-        rollout_random, actor_dtype).  Returns the global rows per step (sum over ranks)."""
+        """``modes``: the FakeEnv / rollout modes of ModelRollout.run (penalty_learned_var, penalty_kind,
+        deterministic, rollout_random, actor_dtype).  Returns the global rows per step (sum over ranks)."""
         import ctypes as C
         import torch.distributed as dist
         from . import _lib as L

@@ -117,7 +117,8 @@ def model_evaluation_metrics(stats):
     """The device statistics ``ModelRollout.evaluate(...)['stats']`` (f64[16]; the first eleven in
     ``MODEL_EVAL_KEYS`` order) as evaluate_rollouts' OrderedDict plus ``penalized-return-average`` (mean
     of the penalized returns, fake_env.py:115), ``penalty-average`` (mean penalty per step taken) and
-    ``terminated-fraction`` (episodes ended by the termination rule before the length cap)."""
+    ``terminated-fraction`` (episodes ended by the termination rule before the length cap).  The penalty is
+    the selected kind's (``fake_env.PENALTY_KINDS``; ``penalty_kind`` of ``ModelRollout.evaluate`` / ``MOPO``)."""
     s = stats.detach().cpu().numpy() if hasattr(stats, 'detach') else np.asarray(stats)
     return OrderedDict((k, float(s[i])) for i, k in enumerate(MODEL_EVAL_KEYS))
 
@@ -148,7 +149,10 @@ def open_loop_metrics(stats):
     after k model steps), ``obs-error-h{k}``, ``penalty-h{k}``, ``covered-h{k}`` (fraction with penalty >= error)
     and ``alive-h{k}`` (segments that reached the step); pooled ``open_loop/error``, ``penalty``,
     ``penalty-error-corr`` (Pearson), ``covered`` and ``termination-mismatch`` (the termination rule on the
-    predicted state against the data's flag)."""
+    predicted state against the data's flag).  ``penalty*`` / ``covered*`` report the selected penalty kind
+    (``fake_env.PENALTY_KINDS``; ``penalty_kind`` of ``ModelRollout.validate`` / ``MOPO``): compared with the
+    error over all outputs for max_aleatoric and ensemble_std, over the obs dims for mean_distance and
+    max_pairwise."""
     s = stats.detach().cpu().numpy() if hasattr(stats, 'detach') else np.asarray(stats)
     K = s.shape[0] - 1
     out = OrderedDict()
@@ -162,17 +166,21 @@ def open_loop_metrics(stats):
 
 
 def open_loop_metrics_numpy(errors, obs_errors, reward_errors, penalties, term_pred, term_data, lengths,
-                            penalty_learned_var=True):
+                            penalty_learned_var=True, penalty_kind=None):
     """The same [K + 1, 16] table from the per-segment host arrays ([K, B]; ``lengths`` [B]): what the device
     reduction must equal.  Entry (k, b) counts when k < lengths[b]; the penalty is compared with ``errors`` for
     the learned-variance penalty (a norm over all outputs) and with ``obs_errors`` for the mean-distance one (a
-    norm over the obs dims).  The correlation is 0 for fewer than two entries or a zero variance; a row
+    norm over the obs dims); ``penalty_kind`` names any of ``fake_env.PENALTY_KINDS`` instead (ensemble_std with
+    ``errors``, max_pairwise with ``obs_errors``).  The correlation is 0 for fewer than two entries or a zero variance; a row
     without entries is all zero."""
     e, eo = np.asarray(errors, np.float64), np.asarray(obs_errors, np.float64)
     er, u = np.asarray(reward_errors, np.float64), np.asarray(penalties, np.float64)
     tp, td = np.asarray(term_pred), np.asarray(term_data)
     K, B = e.shape
     live = np.arange(K)[:, None] < np.asarray(lengths).reshape(1, B)
+    if penalty_kind is not None:
+        from .fake_env import penalty_kind_id
+        penalty_learned_var = penalty_kind_id(penalty_kind) in (1, 3)   # the kinds over all D outputs
     es = e if penalty_learned_var else eo
     table = np.zeros((K + 1, 16))
     for k in range(K + 1):

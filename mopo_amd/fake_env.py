@@ -9,6 +9,9 @@ RNG: ``rng='numpy'`` (default) consumes numpy's global legacy stream exactly lik
 -- ``np.random.normal(size=(E, B, D))`` then ``model.random_inds(B)`` -- so results match the
 reference for the same seed; only the selected member's noise is shipped to the device.
 numpy inputs return numpy outputs; torch CUDA inputs return torch CUDA outputs.
+
+``penalty_kind`` (one of ``PENALTY_KINDS``; not in the reference) names the reward penalty; ``None`` keeps the
+reference's choice by ``penalty_learned_var``.  ``info['penalty']`` carries the selected kind's penalty.
 """
 import numpy as np
 
@@ -16,15 +19,53 @@ from . import _lib as L
 from .static import term_kind_of
 
 
+# The reward penalty u(s, a) of r~ = r - penalty_coeff * u; the index is the C ABI's MOPO_PENALTY_* id.
+# mean_distance and max_aleatoric are the reference's two (penalty_learned_var False / True, fake_env.py:98-110);
+# max_pairwise is the largest pairwise member discrepancy over the observation outputs (MOReL's criterion);
+# ensemble_std the std of the ensemble taken as a mixture over all outputs (aleatoric plus epistemic).
+PENALTY_KINDS = ('mean_distance', 'max_aleatoric', 'max_pairwise', 'ensemble_std')
+
+
+def penalty_kind_id(penalty_kind=None, penalty_learned_var=None):
+    """The MOPO_PENALTY_* id of a penalty choice.  ``penalty_kind`` None: the reference's choice by
+    ``penalty_learned_var`` (True: max_aleatoric, else mean_distance).  A name (or an id) sets the kind; one
+    that contradicts an explicit ``penalty_learned_var=True`` raises ``ValueError``, as does an unknown name."""
+    if penalty_kind is None:
+        return 1 if penalty_learned_var else 0
+    if isinstance(penalty_kind, (int, np.integer)) and not isinstance(penalty_kind, bool) \
+            and 0 <= int(penalty_kind) < len(PENALTY_KINDS):
+        kind = int(penalty_kind)
+    elif penalty_kind in PENALTY_KINDS:
+        kind = PENALTY_KINDS.index(penalty_kind)
+    else:
+        raise ValueError('unknown penalty_kind %r: one of %s' % (penalty_kind, ', '.join(PENALTY_KINDS)))
+    if penalty_learned_var is True and kind != 1:
+        raise ValueError('penalty_kind=%r contradicts penalty_learned_var=True (that is %r)'
+                         % (PENALTY_KINDS[kind], PENALTY_KINDS[1]))
+    return kind
+
+
 class FakeEnv:
     def __init__(self, model, config, penalty_coeff=0., penalty_learned_var=False,
-                 penalty_learned_var_random=False):
+                 penalty_learned_var_random=False, penalty_kind=None):
         self.model = model
         self.config = config
         self.penalty_coeff = penalty_coeff
-        self.penalty_learned_var = penalty_learned_var
+        kind = penalty_kind_id(penalty_kind, penalty_learned_var)
+        self._named_kind = None if penalty_kind is None else kind
+        # readable as before: True only for max_aleatoric (with penalty_kind None: what was passed)
+        self.penalty_learned_var = penalty_learned_var if penalty_kind is None else kind == 1
         self.penalty_learned_var_random = penalty_learned_var_random
         self.term_kind = term_kind_of(config)
+
+    @property
+    def penalty_kind_id(self):
+        """The MOPO_PENALTY_* id: the named kind, else the reference's choice by ``penalty_learned_var``."""
+        return int(bool(self.penalty_learned_var)) if self._named_kind is None else self._named_kind
+
+    @property
+    def penalty_kind(self):
+        return PENALTY_KINDS[self.penalty_kind_id]
 
     def step(self, obs, act, deterministic=False, noise=None, model_inds=None, stream=None):
         import torch
@@ -67,7 +108,7 @@ class FakeEnv:
         args = L.FakeEnvArgs(
             d_obs=L.ptr(o), obs_f64=int(o.dtype == torch.float64), d_act=L.ptr(a), B=B,
             d_noise_sel=L.ptr(noise_sel), d_model_inds=L.ptr(inds), deterministic=int(bool(deterministic)),
-            penalty_coeff=float(self.penalty_coeff), penalty_learned_var=int(bool(self.penalty_learned_var)),
+            penalty_coeff=float(self.penalty_coeff), penalty_learned_var=self.penalty_kind_id,
             term_kind=self.term_kind, d_next_obs=L.ptr(out['next_obs']), d_rewards=L.ptr(out['rew']),
             d_terminals=L.ptr(out['term']), d_penalty=L.ptr(out['penalty']), d_unpenalized=L.ptr(out['unpen']),
             d_info_mean=L.ptr(out['imean']), d_info_std=L.ptr(out['istd']), d_log_prob=L.ptr(out['logp']),

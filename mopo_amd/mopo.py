@@ -37,7 +37,7 @@ class MOPO:
                  n_epochs=1000, n_train_repeat=1, batch_size=256, seed=88, reparameterize=True, max_model_t=None,
                  rollout_random=False, evaluation_environment=None, eval_n_episodes=10, eval_deterministic=True,
                  max_path_length=1000, ensemble_dtype=None, actor_dtype=None, model_eval_episodes=0,
-                 model_eval_length=None, model_val_segments=0, model_val_horizon=None, **kwargs):
+                 model_eval_length=None, model_val_segments=0, model_val_horizon=None, penalty_kind=None, **kwargs):
         """``ensemble_dtype``: the ensemble forward's arithmetic (``mopo_amd.bnn.DTYPES``), default
         ``DEFAULT_ENSEMBLE_DTYPE`` ('bf16x6': the f32 operands split exactly into 3 bf16 parts, 6 bf16
         MFMA products, f32 accumulate; 'fp32' above H = 256: ``bnn.default_ensemble_dtype``); 'fp32' runs
@@ -48,7 +48,10 @@ class MOPO:
         learned model (``_evaluate_in_model``: ``model_eval/*`` diagnostics); 0, the default, runs none.
         ``model_val_segments`` > 0: right after the ensemble is trained, that many segments of at most
         ``model_val_horizon`` (default ``rollout_length``) dataset steps are replayed open-loop through it
-        (``_validate_model``: ``model/open_loop/*`` diagnostics on every epoch's line); 0, the default, runs none."""
+        (``_validate_model``: ``model/open_loop/*`` diagnostics on every epoch's line); 0, the default, runs none.
+        ``penalty_kind``: the reward penalty, one of ``fake_env.PENALTY_KINDS`` (None, the default: the
+        reference's choice by ``penalty_learned_var``); the training rollouts, ``model_eval/*`` and
+        ``model/open_loop/*`` all use it."""
         if kwargs.get('action_prior', 'uniform') != 'uniform':   # mopo.py:364 asserts the uniform prior
             raise AssertionError("MOPO's policy loss supports action_prior='uniform' only (mopo.py:364)")
         self._pool = pool                                   # device SimpleReplayPool of env data
@@ -60,7 +63,7 @@ class MOPO:
                                       load_dir=model_load_dir, deterministic=deterministic,
                                       dtype=ensemble_dtype or default_ensemble_dtype(hidden_dim), seed=seed)   # the run seed (simple_run/main.py:180 set_seed) fixes the init
         self.fake_env = FakeEnv(self._model, static_fns, penalty_coeff=penalty_coeff,
-                                penalty_learned_var=penalty_learned_var)
+                                penalty_learned_var=penalty_learned_var, penalty_kind=penalty_kind)
         self._rollout_schedule = [20, 100, rollout_length, rollout_length]                 # mopo.py:137
         self._model_retain_epochs = model_retain_epochs
         self._model_train_freq = model_train_freq
@@ -143,7 +146,7 @@ class MOPO:
     # -- mopo.py:723-765 (device-resident, perf-mode RNG); ``deterministic`` as mopo.py:558-559 passes it
     def _rollout_model(self, rollout_batch_size, deterministic=None, rollout_key=None, **kwargs):
         key = self._epoch if rollout_key is None else rollout_key
-        modes = dict(penalty_learned_var=self.fake_env.penalty_learned_var,
+        modes = dict(penalty_learned_var=self.fake_env.penalty_learned_var, penalty_kind=self.fake_env.penalty_kind,
                      deterministic=self._deterministic if deterministic is None else deterministic,
                      rollout_random=self._rollout_random)
         env_obs = self._pool.fields['observations'][:self._pool.size]
@@ -264,6 +267,7 @@ class MOPO:
                                           seed=self._seed ^ self.MODEL_EVAL_SEED_XOR, epoch=self._epoch,
                                           pi_hidden=self._pi_hidden, actor_dtype=self._actor_dtype,
                                           penalty_learned_var=self.fake_env.penalty_learned_var,
+                                          penalty_kind=self.fake_env.penalty_kind,
                                           deterministic=self._deterministic)
         return model_evaluation_metrics(out['stats'])
 
@@ -285,7 +289,8 @@ class MOPO:
         ro = ModelRollout(self._model, n, 1)
         out = ro.validate(self._pool, n, self._model_val_horizon, self.fake_env.term_kind, self._model._model_inds,
                           seed=self._seed ^ self.MODEL_VAL_SEED_XOR, epoch=0,
-                          penalty_learned_var=self.fake_env.penalty_learned_var, deterministic=True)
+                          penalty_learned_var=self.fake_env.penalty_learned_var,
+                          penalty_kind=self.fake_env.penalty_kind, deterministic=True)
         return open_loop_metrics(out['stats'])
 
     def train(self, n_epochs=None):
@@ -315,9 +320,10 @@ class MOPO:
 
 def from_config(params, pool, static_fns, model_load_dir=None, **overrides):
     """Build MOPO from ``mopo_amd.config.get_params(...)`` (examples/config/d4rl dicts)."""
-    from .config import DIMS
+    from .config import DIMS, resolve_penalty_kind
     kw = dict(params['kwargs'])
     kw.update(overrides)
+    resolve_penalty_kind(kw)
     obs_dim, act_dim = DIMS[params['domain']]
     kw.setdefault('model_load_dir', model_load_dir)
     return MOPO(pool, static_fns, obs_dim, act_dim, **kw)

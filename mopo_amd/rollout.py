@@ -119,13 +119,15 @@ class ModelRollout:
     def run(self, env_obs, pi_params, pool, batch_size, horizon, term_kind, penalty_coeff, elites,
             seed=0, epoch=0, pi_hidden=256, start_idx=None, eps_act=None, eps_obs=None, model_inds=None,
             staged=False, uid_offset=0, stream=None, step_desc=None, step_hook=None, penalty_learned_var=True,
-            deterministic=False, rollout_random=False, act_uniform=None, actor_dtype=None):
+            deterministic=False, rollout_random=False, act_uniform=None, actor_dtype=None, penalty_kind=None):
         """Returns the device int64[horizon] tensor of rows added per step (steps_added).
         ``step_desc(i)`` / ``step_hook(i, steps)``: per-step staging (see mopo_rollout_run_staged_steps).
         ``penalty_learned_var`` / ``deterministic``: FakeEnv's modes (fake_env.py:69-110; every D4RL
         config uses the learned-var penalty, not deterministic); ``rollout_random``: uniform actions
         (mopo.py:736-738), ``act_uniform`` [horizon, B, A] injects them in parity mode.
-        ``actor_dtype``: 'fp32', 'bf16x6' or 'f16x3' policy forward (default: default_actor_dtype)."""
+        ``actor_dtype``: 'fp32', 'bf16x6' or 'f16x3' policy forward (default: default_actor_dtype).
+        ``penalty_kind``: one of ``fake_env.PENALTY_KINDS`` (None: by ``penalty_learned_var``); 'max_pairwise'
+        and 'ensemble_std' run csrc/penalty.hip behind every ensemble launch when ``penalty_coeff`` != 0."""
         import torch
         dev = env_obs.device
         B = int(batch_size)
@@ -137,7 +139,7 @@ class ModelRollout:
         keep = [steps]
         args = self._args(keep, env_obs, pi_params, B, horizon, term_kind, penalty_coeff, elites, seed, epoch,
                           pi_hidden, start_idx, eps_act, eps_obs, model_inds, uid_offset, steps, penalty_learned_var,
-                          deterministic, rollout_random, act_uniform, actor_dtype, legacy)
+                          deterministic, rollout_random, act_uniform, actor_dtype, legacy, penalty_kind=penalty_kind)
         if step_hook is not None:
             # one call per horizon step into the staging block step_hook(i) names; step_hook(i, steps)
             # is then called after step i is enqueued (multi-GPU: gather step i while i + 1 computes)
@@ -155,9 +157,12 @@ class ModelRollout:
 
     def _args(self, keep, env_obs, pi_params, B, horizon, term_kind, penalty_coeff, elites, seed, epoch, pi_hidden,
               start_idx, eps_act, eps_obs, model_inds, uid_offset, steps, penalty_learned_var, deterministic,
-              rollout_random, act_uniform, actor_dtype, fresh_elites=False):
+              rollout_random, act_uniform, actor_dtype, fresh_elites=False, penalty_kind=None):
         """The C ABI's mopo_rollout_args; every tensor it points to is appended to ``keep``."""
         import torch
+        from .fake_env import penalty_kind_id
+        # a named kind wins over run()'s default penalty_learned_var=True (only FakeEnv refuses a contradiction)
+        kind = penalty_kind_id(penalty_kind, None if penalty_kind is not None else penalty_learned_var)
         dev = env_obs.device
         ekey = (tuple(int(e) for e in np.asarray(elites).ravel()), str(dev))
         if getattr(self, '_elites', (None, None))[0] != ekey or fresh_elites:
@@ -179,20 +184,20 @@ class ModelRollout:
             seed=int(seed) & (2 ** 64 - 1), epoch=int(epoch), uid_offset=int(uid_offset),
             d_eps_act=dptr(eps_act, torch.float32), d_eps_obs=dptr(eps_obs, torch.float64),
             d_model_inds=dptr(model_inds, torch.int32), d_steps=L.ptr(steps),
-            penalty_learned_var=int(bool(penalty_learned_var)), deterministic=int(bool(deterministic)),
+            penalty_learned_var=kind, deterministic=int(bool(deterministic)),
             rollout_random=int(bool(rollout_random)), d_act_uniform=dptr(act_uniform, torch.float32),
             actor_dtype=_ACTOR_DTYPES[actor_dtype or default_actor_dtype(self.model.dtype)])
 
     def evaluate(self, env_obs, pi_params, n_episodes, max_length, term_kind, penalty_coeff, elites,
                  policy_deterministic=True, seed=0, epoch=0, pi_hidden=256, start_idx=None, eps_act=None,
                  eps_obs=None, model_inds=None, uid_offset=0, stream=None, penalty_learned_var=True,
-                 deterministic=False, rollout_random=False, act_uniform=None, actor_dtype=None):
+                 deterministic=False, rollout_random=False, act_uniform=None, actor_dtype=None, penalty_kind=None):
         """Model-based policy evaluation (csrc/rollout_eval.hip): ``n_episodes`` episodes of at most
         ``max_length`` <= 4095 steps of the policy inside the learned model, from env-pool start states, on the
         current stream; nothing enters a pool and numpy's global stream is not drawn from.
         ``policy_deterministic``: tanh(mu) actions (the evaluation policy, mopo.py:481-482), else sampled --
         then the episodes are the trajectories ``run`` visits for the same arguments.  The other arguments
-        are ``run``'s.  Returns device tensors: ``returns`` (unpenalized), ``penalized_returns``,
+        are ``run``'s; the penalty sums and penalized returns are of the selected ``penalty_kind``.  Returns device tensors: ``returns`` (unpenalized), ``penalized_returns``,
         ``penalty_sums`` (f64[n]), ``lengths`` (i32[n]), ``terminated`` (u8[n]), ``steps`` (int64[max_length] live
         episodes per step) and ``stats`` (f64[16], see ``evaluation.model_evaluation_metrics``).  These are
         returns under the model: biased wherever the model is wrong."""
@@ -209,7 +214,7 @@ class ModelRollout:
         keep = list(out.values())
         args = self._args(keep, env_obs, pi_params, n, T, term_kind, penalty_coeff, elites, seed, epoch, pi_hidden,
                           start_idx, eps_act, eps_obs, model_inds, uid_offset, out['steps'], penalty_learned_var,
-                          deterministic, rollout_random, act_uniform, actor_dtype)
+                          deterministic, rollout_random, act_uniform, actor_dtype, penalty_kind=penalty_kind)
         ev = L.EvalArgs(policy_deterministic=int(bool(policy_deterministic)), d_return=L.ptr(out['returns']),
                         d_pen_return=L.ptr(out['penalized_returns']), d_pen_sum=L.ptr(out['penalty_sums']),
                         d_length=L.ptr(out['lengths']), d_terminated=L.ptr(out['terminated']),
@@ -219,7 +224,8 @@ class ModelRollout:
         return out
 
     def validate(self, pool, n_segments, horizon, term_kind, elites, seed=0, epoch=0, start_idx=None, eps_obs=None,
-                 model_inds=None, uid_offset=0, stream=None, penalty_learned_var=True, deterministic=True):
+                 model_inds=None, uid_offset=0, stream=None, penalty_learned_var=True, deterministic=True,
+                 penalty_kind=None):
         """Open-loop model validation (csrc/rollout_val.hip): ``n_segments`` segments of at most ``horizon`` <=
         4095 steps, each from a row of ``pool`` (a ``SimpleReplayPool`` or a ``PoolDesc``), replaying the
         DATASET's actions through the model on the model's own predicted states and comparing every step with
@@ -231,7 +237,9 @@ class ModelRollout:
         ``obs_errors``, ``reward_errors`` (f64[horizon, n]; NaN past a segment's length), ``penalties``
         (f32[horizon, n]), ``term_pred`` / ``term_data`` (u8[horizon, n]; 0xFF past the length), ``lengths``
         (i32[n]), ``end_reasons`` (u8[n]), ``start_rows`` (int64[n]), ``steps`` (int64[horizon] live segments per step) and ``stats``
-        (f64[horizon + 1, 16], see ``evaluation.open_loop_metrics``).  A pool holding the model's own training
+        (f64[horizon + 1, 16], see ``evaluation.open_loop_metrics``).  ``penalty_kind`` (one of
+        ``fake_env.PENALTY_KINDS``, None: by ``penalty_learned_var``) selects the penalty of ``penalties`` and of
+        the statistics; call once per kind on the same segments to compare them.  A pool holding the model's own training
         rows gives an in-distribution, optimistic curve; pass unseen trajectories for a held-out one."""
         import torch
         desc = pool.desc() if not isinstance(pool, L.PoolDesc) else pool
@@ -256,7 +264,7 @@ class ModelRollout:
         # device for _args, and its pointers to it are dropped again below
         args = self._args(keep, out['stats'], 0, n, K, term_kind, 0.0, elites, seed, epoch, 0, start_idx, None,
                           eps_obs, model_inds, uid_offset, out['steps'], penalty_learned_var, deterministic, False,
-                          None, 'fp32')
+                          None, 'fp32', penalty_kind=penalty_kind)
         args.d_env_obs, args.env_size, args.d_steps = None, 0, None
         va = L.ValArgs(d_err=L.ptr(out['errors']), d_err_obs=L.ptr(out['obs_errors']),
                        d_err_rew=L.ptr(out['reward_errors']), d_pen=L.ptr(out['penalties']),

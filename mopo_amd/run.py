@@ -11,11 +11,13 @@ is trained from its initial weights to early stopping first (mopo.py:526-531).
 epoch (``model_eval/*``: the return under the model, not a D4RL score); off by default.
 ``--model-val-segments`` / ``--model-val-horizon``: replay dataset trajectories open-loop through the trained
 model (``model/open_loop/*``: the compounding error and the penalty's calibration); off by default.
+``--penalty-kind``: the reward penalty (mopo_amd.fake_env.PENALTY_KINDS); default: the config's choice.
 """
 import argparse
 import json
 
 from .bnn import DEFAULT_ENSEMBLE_DTYPE, DTYPES
+from .fake_env import PENALTY_KINDS
 
 
 def main(argv=None):
@@ -40,6 +42,9 @@ def main(argv=None):
                         'default: the config kwarg model_val_segments, else 0 = none)')
     p.add_argument('--model-val-horizon', type=int, default=None,
                    help='step cap of those segments, <= 4095 (default: rollout_length)')
+    p.add_argument('--penalty-kind', default=None, choices=PENALTY_KINDS,
+                   help='the reward penalty u of r - penalty_coeff * u (default: the config kwarg penalty_kind, else '
+                        'by its penalty_learned_var: max_aleatoric / mean_distance)')
     a = p.parse_args(argv)
     from .config import DIMS, get_params
     from .loader import restore_pool
@@ -50,7 +55,8 @@ def main(argv=None):
     obs_dim, act_dim = DIMS[params['domain']]
     pool = SimpleReplayPool(obs_dim=obs_dim, act_dim=act_dim, max_size=int(1e6))   # simple_run/base.py:267-272
     restore_pool(pool, a.data)
-    over = {k: v for k, v in (('ensemble_dtype', a.ensemble_dtype), ('actor_dtype', a.actor_dtype)) if v}
+    over = {k: v for k, v in (('ensemble_dtype', a.ensemble_dtype), ('actor_dtype', a.actor_dtype),
+                              ('penalty_kind', a.penalty_kind)) if v}
     over.update((k, v) for k, v in (('model_eval_episodes', a.model_eval_episodes),
                                     ('model_eval_length', a.model_eval_length),
                                     ('model_val_segments', a.model_val_segments),
