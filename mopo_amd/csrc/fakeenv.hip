@@ -147,8 +147,6 @@ extern "C" int mopo_fakeenv_step(mopo_bnn_t hh, const mopo_fakeenv_args* a, void
   MOPO_REQUIRE(!a->d_info_mean == !a->d_info_std, "mopo_fakeenv_step: info_mean/info_std go together");
   hipStream_t s = (hipStream_t)stream;
   FwdArgs f{};
-  const size_t es = a->obs_f64 ? 8 : 4;
-  (void)es;
   f.in = FwdIn{a->d_obs, a->obs_f64, h->O, a->d_act, 0, h->A};
   f.B = a->B;
   f.mean = a->d_ens_mean;

@@ -1,6 +1,8 @@
-// The rollout handle and the pieces of rollout.hip that rollout_eval.hip (model-based policy evaluation) and
-// rollout_val.hip (open-loop validation on dataset trajectories) launch as they are: the start-state gather,
-// the wide models' scaled input rows and the compaction.
+// The rollout handle and what the three device loops over the model share on the host: the training rollout
+// (rollout.hip), the model-based policy evaluation (rollout_eval.hip) and the open-loop validation on dataset
+// trajectories (rollout_val.hip).  One statement of a step's setup (argument checks, FakeEnv modes, the actor
+// pack, the ensemble's and the post kernel's arguments, the wide-input / compaction launches, the live-count
+// read-back), defined in rollout.hip; the device side of the step itself is rollout_post.h.
 #pragma once
 #include "actor.h"
 
@@ -13,7 +15,6 @@ struct Rollout {
   // optional live kernel timing: hipEvents recorded around every launch, per kernel class
   bool profile = false;
   std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> ev;
-  std::vector<hipEvent_t> pool_ev;
   size_t ev_used = 0;
   Bnn* bnn = nullptr;
   int64_t Bmax = 0;
@@ -88,17 +89,57 @@ struct PostArgs {
   int pen_dist, det;
 };
 
-// defined in rollout.hip
-constexpr int START_ROWS = 64, START_TPB = 256;
-__global__ void rollout_start_kernel(const float* env_obs, int64_t env_size, const int64_t* idx_in, int O, int64_t B,
-                                     uint64_t seed, uint32_t step, int64_t uid_offset, double* obs, int64_t* uid,
-                                     int* cnt, int nsplit, int64_t bpart);
-__global__ void rollout_xs_wide_kernel(const double* __restrict__ obs, const float* __restrict__ act, int O, int A,
-                                       const float* __restrict__ mu, const float* __restrict__ sigma, int64_t B,
-                                       const int* __restrict__ d_count, float* __restrict__ xs);
-__global__ void rollout_compact_kernel(int O, const int* blockcnt, const uint8_t* keepf, const int* cnt,
-                                       const double* obs_src, double* obs_dst, const int64_t* uid_src,
-                                       int64_t* uid_dst, int* survivors);
+// FakeEnv's modes for one call: deterministic steps, the mean-distance penalty (computed by the post kernel),
+// a penalty kind >= 2 (penalty.hip, 0: none), and whether any of them needs every member's mean per row
+struct StepModes {
+  bool det, pen_dist;
+  int pen_kind;
+  bool need_all;
+};
+
+// The checks every entry point `who` makes on its arguments: B, term_kind, the penalty kind, the elites (an
+// entry point that runs no policy needs none for deterministic steps) and, with a policy, actor_dtype.
+int rollout_check_args(const Rollout* h, const mopo_rollout_args* a, const char* who, bool policy);
+// The modes of `a` (always_pen: the penalty is computed whatever the coefficient); allocates mean_all /
+// std_all on first use.
+int rollout_modes(Rollout* h, const mopo_rollout_args* a, bool always_pen, StepModes* m);
+// The start states (rollout_start_kernel): a's B rows gathered from env_obs rows idx (NULL: drawn over
+// [0, env_size)) into obs[0], their ids into uid[0], the live counts of the nsplit parts of bpart rows.
+int rollout_start(Rollout* h, const mopo_rollout_args* a, const float* env_obs, int64_t env_size, const int64_t* idx,
+                  int nsplit, int64_t bpart, hipStream_t s);
+// (Re)allocates the handle's fragment-major policy weights for a's width and dtype and packs them on s.
+int rollout_pack_actor(Rollout* h, const mopo_rollout_args* a, hipStream_t s);
+// Horizon step i for rows [off, off + n) of a's batch, live count *cnt, reading obs[oc] / uid[uc]: the fields
+// of the actor's, the ensemble's and the post kernel's arguments that the loops share (no pool, one stream).
+ActorArgs rollout_actor_args(const Rollout* h, const mopo_rollout_args* a, const StepModes& m, int i, int oc, int uc,
+                             int64_t off, int64_t n, int* cnt);
+FwdArgs rollout_fwd_args(const Rollout* h, const StepModes& m, int oc, int64_t off, int64_t n, int* cnt, float* xs);
+PostArgs rollout_post_args(const Rollout* h, const mopo_rollout_args* a, const StepModes& m, int i, int oc, int uc,
+                           int64_t off, int* cnt, bool compact);
+// A wide model's scaled input rows (rollout_xs_wide_kernel) behind whatever wrote act.
+int rollout_xs_wide(const Rollout* h, int oc, int64_t off, int64_t n, const int* cnt, float* xs, hipStream_t s);
+// Compaction of B launch rows: the chunk counts zeroed before the post kernel, and behind it
+// rollout_compact_kernel from obs[oc ^ 1] / uid[uc] into obs[oc] / uid[uc ^ 1], survivors to cnt[1].
+int rollout_zero_chunks(Rollout* h, int64_t B, hipStream_t s);
+int rollout_compact(Rollout* h, int64_t B, int oc, int uc, hipStream_t s);
+// MOPO_EVAL_POLL=<steps between two read-backs of the live count> (0: never read it back); default 32.
+// Read at every call (tests compare settings in one process); the results do not depend on it.
+int rollout_poll_steps();
+// Reads the live count back (synchronises s); *none: no row is alive, the remaining steps would all return on
+// the zero count.
+int rollout_none_alive(Rollout* h, hipStream_t s, bool* none);
+
+// Carves one allocation into n arrays of sz[i] bytes at 256-byte-aligned offsets off[i] (an array with
+// given[i] set takes no room); returns the allocation's size.
+inline size_t carve(const size_t* sz, int n, size_t* off, void* const* given = nullptr) {
+  size_t tot = 0;
+  for (int i = 0; i < n; ++i) {
+    off[i] = tot;
+    if (!given || !given[i]) tot += (sz[i] + 255) & ~(size_t)255;
+  }
+  return tot;
+}
+
 // defined in rollout_eval.hip
 __global__ void rollout_eval_advance_kernel(int* cnt, int64_t* steps, int i);
 

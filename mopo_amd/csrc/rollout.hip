@@ -11,7 +11,7 @@
 //   step_advance      steps_added / pool pointer & size (mopo.py:748; flexible_replay_pool.py:45-48)
 #include "mlp_tile.h"
 #include "penalty.h"
-#include "rollout.h"
+#include "rollout_post.h"
 
 namespace mopo {
 
@@ -42,6 +42,7 @@ struct KTimer {
 // Start states (mopo.py:740-741): a block's 64 rows draw their source rows first (one thread each), then the
 // block copies the 64 x O observations element-wise, so the f64 stores of consecutive threads are contiguous
 // (one thread per row, each storing its 136-B row, took 26 us per 100k rows)
+constexpr int START_ROWS = 64, START_TPB = 256;
 __global__ __launch_bounds__(START_TPB) void rollout_start_kernel(const float* env_obs, int64_t env_size,
                                                                   const int64_t* idx_in, int O, int64_t B,
                                                                   uint64_t seed, uint32_t step, int64_t uid_offset,
@@ -103,13 +104,9 @@ __global__ __launch_bounds__(256) void rollout_xs_wide_kernel(const double* __re
   *reinterpret_cast<f32x4*>(xs + row * XS_STRIDE_WIDE + 4 * q) = v;
 }
 
-// FakeEnv post-processing of one horizon step (fake_env.py:66-115) for POST_RPB rows per block, one
-// 32-lane group per row and one lane per output dim d < D = O + 1: every load and store of the row's
-// D values is contiguous across its lanes, and each lane draws only its own normal (Philox block
-// d / 4, Box-Muller pair (d % 4) / 2: the same numbers the per-row order gives).  The row's next
-// observation is assembled in LDS for the termination function.  With compaction, the kept rows of
-// each PB-row chunk are counted into blockcnt (zeroed before the launch).
-constexpr int POST_RPB = 8;
+// FakeEnv post-processing of one horizon step (rollout_post.h) for POST_RPB rows per block, one 32-lane group
+// per row; the row's next observation is assembled in LDS for the termination function.  Its own part: the
+// next_obs / rew / term half of the pool row (fake_env.py:90-115; mopo.py:750-751).
 __global__ __launch_bounds__(256) void rollout_post_kernel(const PostArgs a) {
   __shared__ double srow[POST_RPB][33];
   __shared__ int kept[POST_RPB];
@@ -119,51 +116,8 @@ __global__ __launch_bounds__(256) void rollout_post_kernel(const PostArgs a) {
   const int64_t count = *a.cnt;
   const bool live = row < count;
   const bool on = live && sub < D;
-  double s = 0.0;
-  // member e's mean of this lane's dim after the residual add, in f32 as the reference's in-place
-  // ensemble_model_means[:, :, 1:] += obs (fake_env.py:66)
-  const double ob = on && sub >= 1 ? a.obs[row * O + sub - 1] : 0.0;
-  auto member_mean = [&](int e) {
-    const float m = a.mean_all[((int64_t)e * a.all_stride + row) * D + sub];
-    return sub >= 1 ? (float)((double)m + ob) : m;
-  };
-  float pen_d = 0.f;
-  if (a.pen_dist) {  // max_e || mean_e - mean_e' mean_e' || over the obs dims (fake_env.py:98-108)
-    float sum = 0.f;
-    if (on && sub >= 1)
-      for (int e = 0; e < a.E; ++e) sum += member_mean(e);
-    const float avg = sum / (float)a.E;                           // np.mean(axis=0), f32
-    for (int e = 0; e < a.E; ++e) {
-      const float dd = on && sub >= 1 ? member_mean(e) - avg : 0.f;
-      float q = dd * dd;
-#pragma unroll
-      for (int o = 16; o >= 1; o >>= 1) q += __shfl_xor(q, o);       // the row's 32-lane group
-      pen_d = fmaxf(pen_d, sqrtf(q));
-    }
-  }
-  if (on && a.det) {  // samples = mean over ALL members of the means (fake_env.py:69-70, 84-86)
-    float acc = 0.f;
-    for (int e = 0; e < a.E; ++e) acc += member_mean(e);
-    s = (double)(acc / (float)a.E);
-    srow[rl][sub] = s;
-  } else if (on) {
-    float m = a.mean_sel[row * D + sub];
-    if (sub >= 1) m = (float)((double)m + ob);                      // fake_env.py:66
-    double e;
-    if (a.eps) {
-      e = a.eps[row * D + sub];
-    } else {  // Philox normal `sub` of the row's stream (perf mode of fake_env.py:72)
-      const int64_t u = a.uid[row];
-      u32x4 c{(uint32_t)u, (uint32_t)((uint64_t)u >> 32) ^ ((uint32_t)(sub >> 2) << 20), a.step, RNG_OBS_NOISE};
-      u32x4 r = philox(c, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
-      float z0, z1;
-      if (sub & 2) box_muller(r.z, r.w, z0, z1);
-      else box_muller(r.x, r.y, z0, z1);
-      e = (double)((sub & 1) ? z1 : z0);
-    }
-    s = (double)m + e * (double)a.std_sel[row * D + sub];          // fake_env.py:72
-    srow[rl][sub] = s;
-  }
+  float pen_d;
+  const double s = post_group_step(a, row, sub, on, srow[rl], pen_d);
   __syncthreads();
   const int64_t pos = a.stage_base >= 0 ? a.stage_base + row
                                         : (a.pool.d_state[0] + a.pool_off + row) % a.pool.max_size;
@@ -174,25 +128,15 @@ __global__ __launch_bounds__(256) void rollout_post_kernel(const PostArgs a) {
   if (sub == 0) {
     bool keep = false;
     if (live) {
-      const bool term = term_fn(a.term_kind, &srow[rl][1], O);     // fake_env.py:91
-      const float pen = a.pen_dist ? pen_d : __uint_as_float(a.pen[row]);
-      const double pr = a.coeff != 0.f ? s - (double)a.coeff * (double)pen : s;   // fake_env.py:115
-      a.pool.d_rew[pos] = (float)pr;                               // rewards = samples[:, :1] - c * penalty
-      a.pool.d_term[pos] = term ? 1 : 0;
-      keep = !term;
+      const PostVerdict v = post_verdict(a, row, srow[rl], s, pen_d);
+      a.pool.d_rew[pos] = (float)v.pr;
+      a.pool.d_term[pos] = v.term ? 1 : 0;
+      keep = !v.term;
       if (a.keep) a.keep[row] = keep ? 1 : 0;
     }
     kept[rl] = keep ? 1 : 0;
   }
-  if (a.blockcnt) {
-    __syncthreads();
-    if (tid == 0) {
-      int t = 0;
-#pragma unroll
-      for (int i = 0; i < POST_RPB; ++i) t += kept[i];
-      if (t) atomicAdd(a.blockcnt + (int64_t)blockIdx.x * POST_RPB / PB, t);  // PB % POST_RPB == 0
-    }
-  }
+  if (a.blockcnt) post_count_kept<POST_RPB>(kept, a.blockcnt, (int64_t)blockIdx.x * POST_RPB);
 }
 
 // The same post-processing for the common case (sampled steps, max-aleatoric penalty: neither pen_dist
@@ -219,19 +163,7 @@ __global__ __launch_bounds__(1024) void rollout_post_flat_kernel(const PostArgs 
   if (on) {
     float m = a.mean_sel[row * D + sub];
     if (sub >= 1) m = (float)((double)m + a.obs[row * O + sub - 1]);    // fake_env.py:66
-    double e;
-    if (a.eps) {
-      e = a.eps[row * D + sub];
-    } else {  // Philox normal `sub` of the row's stream (perf mode of fake_env.py:72)
-      const int64_t u = a.uid[row];
-      u32x4 c{(uint32_t)u, (uint32_t)((uint64_t)u >> 32) ^ ((uint32_t)(sub >> 2) << 20), a.step, RNG_OBS_NOISE};
-      u32x4 r = philox(c, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
-      float z0, z1;
-      if (sub & 2) box_muller(r.z, r.w, z0, z1);
-      else box_muller(r.x, r.y, z0, z1);
-      e = (double)((sub & 1) ? z1 : z0);
-    }
-    s = (double)m + e * (double)a.std_sel[row * D + sub];              // fake_env.py:72
+    s = post_sample(a, row, D, sub, m);
     srow[rl][sub] = s;
   }
   __syncthreads();
@@ -255,24 +187,7 @@ __global__ __launch_bounds__(1024) void rollout_post_flat_kernel(const PostArgs 
     }
     kept[tid] = keep ? 1 : 0;
   }
-  if (a.blockcnt) {
-    __syncthreads();
-    if (tid == 0) {
-      int t = 0;
-#pragma unroll
-      for (int i = 0; i < POSTF_ROWS; ++i) t += kept[i];
-      if (t) atomicAdd(a.blockcnt + r0 / PB, t);
-    }
-  }
-}
-
-// MOPO_POST_FLAT=0 (A/B): the 32-lane-per-row post kernel for every step
-static int post_flat() {
-  static const int v = [] {
-    const char* e = std::getenv("MOPO_POST_FLAT");
-    return e ? std::atoi(e) : 1;
-  }();
-  return v;
+  if (a.blockcnt) post_count_kept<POSTF_ROWS>(kept, a.blockcnt, r0);
 }
 
 __global__ __launch_bounds__(PB) void rollout_compact_kernel(int O, const int* blockcnt, const uint8_t* keepf,
@@ -344,20 +259,153 @@ static int split_parts() {  // MOPO_ROLLOUT_SPLIT=<parts> (0 or 1: one stream); 
   return v;
 }
 
+int rollout_start(Rollout* h, const mopo_rollout_args* a, const float* env_obs, int64_t env_size, const int64_t* idx,
+                  int nsplit, int64_t bpart, hipStream_t s) {
+  hipLaunchKernelGGL(rollout_start_kernel, dim3((unsigned)((a->B + START_ROWS - 1) / START_ROWS)), dim3(START_TPB), 0,
+                     s, env_obs, env_size, idx, h->bnn->O, a->B, a->seed, a->epoch * 4096u, a->uid_offset, h->obs[0],
+                     h->uid[0], h->cnt, nsplit, bpart);
+  MOPO_HIP(hipGetLastError());
+  return 0;
+}
+
+int rollout_check_args(const Rollout* h, const mopo_rollout_args* a, const char* who, bool policy) {
+  const std::string w(who);
+  MOPO_REQUIRE(a->B >= 0 && a->B <= h->Bmax, w + ": B exceeds the handle's max_batch");
+  MOPO_REQUIRE(a->term_kind >= 0 && a->term_kind < MOPO_TERM_KINDS, w + ": unknown term_kind");
+  MOPO_REQUIRE(a->penalty_learned_var >= 0 && a->penalty_learned_var < MOPO_PENALTY_KINDS, w + kPenaltyKindMsg);
+  MOPO_REQUIRE((!policy && a->deterministic) || a->d_model_inds || (a->d_elites && a->n_elites > 0),
+               w + ": elites required");
+  MOPO_REQUIRE(!policy || a->actor_dtype == DT_FP32 || a->actor_dtype == DT_F16X3 || a->actor_dtype == DT_BF16X6,
+               w + ": actor_dtype must be 0 (fp32), 3 (bf16x6) or 4 (f16x3)");
+  return 0;
+}
+
+int rollout_modes(Rollout* h, const mopo_rollout_args* a, bool always_pen, StepModes* m) {
+  const bool pen = always_pen || a->penalty_coeff != 0.f;
+  m->det = a->deterministic != 0;
+  m->pen_dist = a->penalty_learned_var == 0 && pen;
+  // kinds >= 2 (penalty.hip): every member's mean and std, reduced by one kernel behind the ensemble
+  m->pen_kind = a->penalty_learned_var >= MOPO_PENALTY_MAX_PAIRWISE && pen ? a->penalty_learned_var : 0;
+  // every member's mean per row is needed by the mean-distance penalty and by deterministic steps
+  m->need_all = m->det || m->pen_dist || m->pen_kind;
+  if (m->need_all && !h->mean_all)
+    MOPO_HIP(hipMalloc(&h->mean_all, (size_t)h->bnn->E * h->Bmax * (h->bnn->O + 1) * sizeof(float)));
+  if (m->pen_kind && rollout_penalty_alloc(h)) return -1;
+  return 0;
+}
+
+int rollout_pack_actor(Rollout* h, const mopo_rollout_args* a, hipStream_t s) {
+  const int O = h->bnn->O, A = h->bnn->A;
+  const int f16 = a->actor_dtype == DT_F16X3 ? 1 : (a->actor_dtype == DT_BF16X6 ? 2 : 0);   // pack_actor's split
+  if (!h->wpk || h->wpk_hp != a->pi_hidden || h->wpk_f16 != f16) {
+    if (h->wpk) (void)hipFree(h->wpk);
+    h->wpk = nullptr;   // a failed allocation leaves nothing for mopo_rollout_destroy to free again
+    MOPO_HIP(hipMalloc(&h->wpk, actor_packed_floats(O, a->pi_hidden, f16) * sizeof(float)));
+    h->wpk_hp = a->pi_hidden;
+    h->wpk_f16 = f16;
+  }
+  return pack_actor(a->d_pi_params, O, A, a->pi_hidden, h->wpk, s, f16);
+}
+
+ActorArgs rollout_actor_args(const Rollout* h, const mopo_rollout_args* a, const StepModes& m, int i, int oc, int uc,
+                             int64_t off, int64_t n, int* cnt) {
+  const Bnn* bnn = h->bnn;
+  const int O = bnn->O, A = bnn->A;
+  const int64_t at = (int64_t)i * a->B + off;   // the rows' place in the injected [horizon][B] streams
+  ActorArgs aa{};
+  aa.P = a->d_pi_params; aa.Wpk = h->wpk; aa.O = O; aa.A = A; aa.Hp = a->pi_hidden;
+  aa.obs = h->obs[oc] + off * O; aa.obs_f64 = 1; aa.B = n; aa.d_count = cnt;
+  aa.eps = a->d_eps_act ? a->d_eps_act + at * A : nullptr;
+  aa.seed = a->seed; aa.step = a->epoch * 4096u + 1 + i; aa.d_uid = h->uid[uc] + off;
+  aa.act = h->act + off * A;
+  aa.stage_base = -1;   // no pool (pool_act NULL): the obs / act half-row is not written anywhere
+  aa.pen_zero = h->pen + off;
+  aa.sel_out = m.det ? nullptr : h->sel + off;
+  aa.sel_in = a->d_model_inds ? a->d_model_inds + at : nullptr;
+  aa.rand_act = a->rollout_random;
+  aa.dtype = a->actor_dtype;
+  aa.alone = 1;
+  aa.act_uni = a->d_act_uniform ? a->d_act_uniform + at * A : nullptr;
+  aa.elites = a->d_elites; aa.n_elites = a->n_elites;
+  // internal.h bnn_wide: 64-slot xs rows, written behind the actor (rollout_xs_wide) instead of by it
+  aa.xs = bnn->dev.KG0 > 2 ? nullptr : h->xs + off * xs_stride(bnn->dev.KG0);
+  aa.xs_mu = bnn->dev.mu; aa.xs_sigma = bnn->dev.sigma; aa.xs_in = bnn->dev.IN;
+  return aa;
+}
+
+FwdArgs rollout_fwd_args(const Rollout* h, const StepModes& m, int oc, int64_t off, int64_t n, int* cnt, float* xs) {
+  const int O = h->bnn->O, A = h->bnn->A, D = O + 1;
+  FwdArgs f{};
+  f.in = FwdIn{h->obs[oc] + off * O, 1, O, h->act + off * A, 0, A};
+  f.B = n; f.d_count = cnt; f.xs = xs;
+  f.pen_bits = h->pen + off; f.sel = m.det ? nullptr : h->sel + off; f.mean_sel = h->mean_sel + off * D;
+  f.std_sel = h->std_sel + off * D;
+  f.mean_all = m.need_all ? h->mean_all + off * D : nullptr;
+  f.std_all = m.pen_kind ? h->std_all + off * D : nullptr;
+  f.all_stride = h->Bmax;
+  return f;
+}
+
+PostArgs rollout_post_args(const Rollout* h, const mopo_rollout_args* a, const StepModes& m, int i, int oc, int uc,
+                           int64_t off, int* cnt, bool compact) {
+  const int O = h->bnn->O, D = O + 1;
+  PostArgs pa{};
+  pa.O = O; pa.cnt = cnt; pa.obs = h->obs[oc] + off * O; pa.uid = h->uid[uc] + off;
+  pa.mean_sel = h->mean_sel + off * D; pa.std_sel = h->std_sel + off * D; pa.pen = h->pen + off;
+  pa.eps = a->d_eps_obs ? a->d_eps_obs + ((int64_t)i * a->B + off) * D : nullptr;
+  pa.seed = a->seed; pa.step = a->epoch * 4096u + 1 + i; pa.coeff = a->penalty_coeff; pa.term_kind = a->term_kind;
+  pa.obs_next = h->obs[oc ^ 1] + off * O; pa.keep = compact ? h->keep : nullptr;
+  pa.blockcnt = compact ? h->blockcnt : nullptr;
+  pa.stage_base = -1;
+  pa.mean_all = m.need_all ? h->mean_all + off * D : nullptr; pa.E = h->bnn->E; pa.all_stride = h->Bmax;
+  pa.pen_dist = m.pen_dist; pa.det = m.det;
+  return pa;
+}
+
+int rollout_xs_wide(const Rollout* h, int oc, int64_t off, int64_t n, const int* cnt, float* xs, hipStream_t s) {
+  const Bnn* bnn = h->bnn;
+  hipLaunchKernelGGL(rollout_xs_wide_kernel, dim3(ceil_div((int)n, 16)), dim3(256), 0, s, h->obs[oc] + off * bnn->O,
+                     h->act + off * bnn->A, bnn->O, bnn->A, bnn->dev.mu, bnn->dev.sigma, n, cnt, xs);
+  MOPO_HIP(hipGetLastError());
+  return 0;
+}
+
+int rollout_zero_chunks(Rollout* h, int64_t B, hipStream_t s) {
+  MOPO_HIP(hipMemsetAsync(h->blockcnt, 0, (size_t)ceil_div((int)B, PB) * sizeof(int), s));
+  return 0;
+}
+
+int rollout_compact(Rollout* h, int64_t B, int oc, int uc, hipStream_t s) {
+  hipLaunchKernelGGL(rollout_compact_kernel, dim3(ceil_div((int)B, PB)), dim3(PB), 0, s, h->bnn->O, h->blockcnt,
+                     h->keep, h->cnt, h->obs[oc ^ 1], h->obs[oc], h->uid[uc], h->uid[uc ^ 1], h->cnt + 1);
+  MOPO_HIP(hipGetLastError());
+  return 0;
+}
+
+int rollout_poll_steps() {
+  const char* e = std::getenv("MOPO_EVAL_POLL");
+  const int n = e ? std::atoi(e) : 32;
+  return n < 0 ? 0 : n;
+}
+
+int rollout_none_alive(Rollout* h, hipStream_t s, bool* none) {
+  int live = 0;
+  MOPO_HIP(hipMemcpyAsync(&live, h->cnt, sizeof(int), hipMemcpyDeviceToHost, s));
+  MOPO_HIP(hipStreamSynchronize(s));
+  *none = live == 0;
+  return 0;
+}
+
 // Horizon steps [i0, i1) of one rollout.  i0 == 0 draws the start states and repacks the policy;
 // later ranges continue from the state the previous call left (obs ping-pong, live counts).  Staged
 // rows of step i go to rows (i - i0) * B of the staging descriptor.
 static int run_impl(Rollout* h, const mopo_rollout_args* a, const mopo_pool_desc* p, bool staged, int i0, int i1,
                     hipStream_t s) {
   MOPO_REQUIRE(a && p, "rollout: NULL argument");
-  MOPO_REQUIRE(a->B >= 0 && a->B <= h->Bmax, "rollout: B exceeds the handle's max_batch");
+  if (rollout_check_args(h, a, "rollout", true)) return -1;
   MOPO_REQUIRE(a->horizon >= 0 && a->horizon <= h->Hmax, "rollout: horizon exceeds max_horizon");
-  MOPO_REQUIRE(a->term_kind >= 0 && a->term_kind < MOPO_TERM_KINDS, "rollout: unknown term_kind");
-  MOPO_REQUIRE(a->penalty_learned_var >= 0 && a->penalty_learned_var < MOPO_PENALTY_KINDS,
-               std::string("rollout") + kPenaltyKindMsg);
   MOPO_REQUIRE(a->d_env_obs && a->env_size > 0, "rollout: empty env pool");
   MOPO_REQUIRE(a->d_pi_params, "rollout: NULL policy params");
-  MOPO_REQUIRE(a->d_model_inds || (a->d_elites && a->n_elites > 0), "rollout: elites required");
   MOPO_REQUIRE(p->d_obs && p->d_act && p->d_rew && p->d_term && p->d_next_obs, "rollout: NULL pool field");
   MOPO_REQUIRE(staged || p->d_state, "rollout: pool state required");
   MOPO_REQUIRE(a->d_steps, "rollout: d_steps output required");
@@ -366,10 +414,11 @@ static int run_impl(Rollout* h, const mopo_rollout_args* a, const mopo_pool_desc
   MOPO_REQUIRE(!staged || p->max_size >= (int64_t)(i1 - i0) * a->B, "rollout: staging buffer too small");
   if (a->B == 0 || a->horizon == 0 || i0 == i1) return 0;
   Bnn* bnn = h->bnn;
-  const int O = bnn->O, A = bnn->A, D = O + 1;
+  const int O = bnn->O, D = O + 1;
   const int64_t B = a->B;
-  const int nblk = ceil_div((int)B, PB);
-  const uint32_t step0 = a->epoch * 4096u;
+  // MOPO_POST_FLAT=0 (A/B): the 32-lane-per-row post kernel for every step.  Read at every call, as MOPO_EVAL_POLL
+  const char* pf = std::getenv("MOPO_POST_FLAT");
+  const bool post_flat = pf ? std::atoi(pf) != 0 : true;
   // live rows are compacted between steps (mopo.py:758); a one-step rollout never needs it: its
   // rows, terminal or not, all enter the pool (mopo.py:750-751) and no next step reads them
   const bool compact = a->term_kind != MOPO_TERM_HALFCHEETAH && a->horizon > 1;
@@ -388,104 +437,50 @@ static int run_impl(Rollout* h, const mopo_rollout_args* a, const mopo_pool_desc
     h->oc = 0;
     h->uc = 0;
     KTimer t(h, KC_START, s);
-    hipLaunchKernelGGL(rollout_start_kernel, dim3((unsigned)((B + START_ROWS - 1) / START_ROWS)), dim3(START_TPB), 0, s,
-                       a->d_env_obs, a->env_size,
-                       a->d_start_idx, O, B, a->seed, step0, a->uid_offset, h->obs[0], h->uid[0], h->cnt, nsplit,
-                       bpart);
+    if (rollout_start(h, a, a->d_env_obs, a->env_size, a->d_start_idx, nsplit, bpart, s)) return -1;
   }
   if (i0 == 0) {
-    MOPO_HIP(hipGetLastError());
-    MOPO_REQUIRE(a->actor_dtype == DT_FP32 || a->actor_dtype == DT_F16X3 || a->actor_dtype == DT_BF16X6,
-                 "rollout: actor_dtype must be 0 (fp32), 3 (bf16x6) or 4 (f16x3)");
-    const int f16 = a->actor_dtype == DT_F16X3 ? 1 : (a->actor_dtype == DT_BF16X6 ? 2 : 0);   // pack_actor's split
-    if (!h->wpk || h->wpk_hp != a->pi_hidden || h->wpk_f16 != f16) {
-      if (h->wpk) (void)hipFree(h->wpk);
-      MOPO_HIP(hipMalloc(&h->wpk, actor_packed_floats(O, a->pi_hidden, f16) * sizeof(float)));
-      h->wpk_hp = a->pi_hidden;
-      h->wpk_f16 = f16;
-    }
     KTimer t(h, KC_START, s);
-    if (pack_actor(a->d_pi_params, O, A, a->pi_hidden, h->wpk, s, f16)) return -1;
+    if (rollout_pack_actor(h, a, s)) return -1;
   }
-  // every member's mean per row is needed by the mean-distance penalty and by deterministic steps
-  const bool det = a->deterministic != 0;
-  const bool pen_dist = a->penalty_learned_var == 0 && a->penalty_coeff != 0.f;
-  // kinds >= 2 (penalty.hip): every member's mean and std, reduced by one kernel behind the ensemble
-  const int pen_kind = a->penalty_learned_var >= MOPO_PENALTY_MAX_PAIRWISE && a->penalty_coeff != 0.f
-                           ? a->penalty_learned_var : 0;
-  const bool need_all = det || pen_dist || pen_kind;
-  if (need_all && !h->mean_all)
-    MOPO_HIP(hipMalloc(&h->mean_all, (size_t)bnn->E * h->Bmax * D * sizeof(float)));
-  if (pen_kind && rollout_penalty_alloc(h)) return -1;
+  StepModes m;
+  if (rollout_modes(h, a, false, &m)) return -1;
   MOPO_REQUIRE(!a->rollout_random || a->d_act_uniform || !a->d_eps_act,
                "rollout: parity mode with rollout_random needs the injected uniforms (d_act_uniform)");
   int oc = h->oc, uc = h->uc;
   // one horizon step for rows [off, off + n) of the batch (live count in *cnt) on stream ss
   auto step_rows = [&](int i, int64_t off, int64_t n, int* cnt, hipStream_t ss, hipEvent_t after_actor) -> int {
-    const uint32_t st = step0 + 1 + i;
-    ActorArgs aa{};
-    aa.P = a->d_pi_params; aa.Wpk = h->wpk; aa.O = O; aa.A = A; aa.Hp = a->pi_hidden;
-    aa.obs = h->obs[oc] + off * O; aa.obs_f64 = 1; aa.B = n; aa.d_count = cnt;
-    aa.eps = a->d_eps_act ? a->d_eps_act + ((int64_t)i * B + off) * A : nullptr;
-    aa.seed = a->seed; aa.step = st; aa.d_uid = h->uid[uc] + off;
-    aa.act = h->act + off * A;
+    ActorArgs aa = rollout_actor_args(h, a, m, i, oc, uc, off, n, cnt);
     aa.pool_obs = p->d_obs; aa.pool_act = p->d_act; aa.pool_state = p->d_state; aa.pool_max = p->max_size;
     aa.stage_base = staged ? (int64_t)(i - i0) * B + off : -1;
     aa.pool_off = batched_advance ? (int64_t)(i - i0) * B + off : 0;
-    aa.pen_zero = h->pen + off;
-    aa.sel_out = det ? nullptr : h->sel + off;
-    aa.sel_in = a->d_model_inds ? a->d_model_inds + (int64_t)i * B + off : nullptr;
-    aa.rand_act = a->rollout_random;
-    aa.dtype = a->actor_dtype;
     aa.alone = !split;
-    aa.act_uni = a->d_act_uniform ? a->d_act_uniform + ((int64_t)i * B + off) * A : nullptr;
-    aa.elites = a->d_elites; aa.n_elites = a->n_elites;
-    const bool wide = bnn->dev.KG0 > 2;   // internal.h bnn_wide: 64-slot xs rows, written behind the actor
+    const bool wide = bnn->dev.KG0 > 2;
     float* xs = h->xs + off * xs_stride(bnn->dev.KG0);
-    aa.xs = wide ? nullptr : xs; aa.xs_mu = bnn->dev.mu; aa.xs_sigma = bnn->dev.sigma; aa.xs_in = bnn->dev.IN;
     {
       KTimer t(h, KC_ACTOR, ss);
       if (launch_actor(aa, ss)) return -1;
-      if (wide) {
-        hipLaunchKernelGGL(rollout_xs_wide_kernel, dim3(ceil_div((int)n, 16)), dim3(256), 0, ss, h->obs[oc] + off * O,
-                           h->act + off * A, O, A, bnn->dev.mu, bnn->dev.sigma, n, cnt, xs);
-        MOPO_HIP(hipGetLastError());
-      }
+      if (wide && rollout_xs_wide(h, oc, off, n, cnt, xs, ss)) return -1;
     }
     if (after_actor) MOPO_HIP(hipEventRecord(after_actor, ss));
 
-    FwdArgs f{};
-    f.in = FwdIn{h->obs[oc] + off * O, 1, O, h->act + off * A, 0, A};
-    f.B = n; f.d_count = cnt; f.xs = xs;
-    f.pen_bits = h->pen + off; f.sel = det ? nullptr : h->sel + off; f.mean_sel = h->mean_sel + off * D;
-    f.std_sel = h->std_sel + off * D;
-    f.mean_all = need_all ? h->mean_all + off * D : nullptr;
-    f.std_all = pen_kind ? h->std_all + off * D : nullptr;
-    f.all_stride = h->Bmax;
+    const FwdArgs f = rollout_fwd_args(h, m, oc, off, n, cnt, xs);
     {
       KTimer t(h, KC_BNN, ss);
       if (launch_bnn_fwd(bnn, FWD_ROLLOUT, f, ss)) return -1;
     }
-    if (pen_kind) {
+    if (m.pen_kind) {
       KTimer t(h, KC_PENALTY, ss);
-      if (rollout_penalty(h, pen_kind, off, n, cnt, ss)) return -1;
+      if (rollout_penalty(h, m.pen_kind, off, n, cnt, ss)) return -1;
     }
 
-    PostArgs pa{};
-    pa.O = O; pa.cnt = cnt; pa.obs = h->obs[oc] + off * O; pa.uid = h->uid[uc] + off;
-    pa.mean_sel = h->mean_sel + off * D; pa.std_sel = h->std_sel + off * D; pa.pen = h->pen + off;
-    pa.eps = a->d_eps_obs ? a->d_eps_obs + ((int64_t)i * B + off) * D : nullptr;
-    pa.seed = a->seed; pa.step = st; pa.coeff = a->penalty_coeff; pa.term_kind = a->term_kind;
-    pa.obs_next = h->obs[oc ^ 1] + off * O; pa.keep = compact ? h->keep : nullptr;
-    pa.blockcnt = compact ? h->blockcnt : nullptr;
-    pa.pool = *p; pa.stage_base = staged ? (int64_t)(i - i0) * B + off : -1;
-    pa.pool_off = batched_advance ? (int64_t)(i - i0) * B + off : 0;
-    pa.mean_all = f.mean_all; pa.E = bnn->E; pa.all_stride = h->Bmax; pa.pen_dist = pen_dist; pa.det = det;
+    PostArgs pa = rollout_post_args(h, a, m, i, oc, uc, off, cnt, compact);
+    pa.pool = *p; pa.stage_base = aa.stage_base; pa.pool_off = aa.pool_off;
     {
       KTimer t(h, KC_POST, ss);
       // with compaction the post kernel adds each block's kept rows into its PB-row chunk count
-      if (compact) MOPO_HIP(hipMemsetAsync(h->blockcnt, 0, (size_t)nblk * sizeof(int), ss));
-      if (post_flat() && !pen_dist && !det && D <= POSTF_MAXD)
+      if (compact && rollout_zero_chunks(h, B, ss)) return -1;
+      if (post_flat && !m.pen_dist && !m.det && D <= POSTF_MAXD)
         hipLaunchKernelGGL(rollout_post_flat_kernel, dim3(ceil_div((int)n, POSTF_ROWS)),
                            dim3((POSTF_ROWS * D + 63) / 64 * 64), 0, ss, pa);
       else
@@ -528,9 +523,7 @@ static int run_impl(Rollout* h, const mopo_rollout_args* a, const mopo_pool_desc
       if (step_rows(i, 0, B, h->cnt, s, nullptr)) return -1;
       if (compact) {
         KTimer t(h, KC_COMPACT, s);
-        hipLaunchKernelGGL(rollout_compact_kernel, dim3(nblk), dim3(PB), 0, s, O, h->blockcnt, h->keep, h->cnt,
-                           h->obs[oc ^ 1], h->obs[oc], h->uid[uc], h->uid[uc ^ 1], h->cnt + 1);
-        MOPO_HIP(hipGetLastError());
+        if (rollout_compact(h, B, oc, uc, s)) return -1;
         uc ^= 1;
       } else {
         oc ^= 1;
@@ -572,9 +565,8 @@ extern "C" int mopo_rollout_create(mopo_rollout_t* out, mopo_bnn_t bnn, int64_t 
   size_t sz[] = {(size_t)B * O * 8, (size_t)B * O * 8, (size_t)B * 8, (size_t)B * 8, (size_t)B * A * 4,
                  (size_t)B * 4,     (size_t)B * 4,     (size_t)B * D * 4, (size_t)B * D * 4, (size_t)B,
                  (size_t)nblk * 4,  32,                (size_t)B * xs_stride(b->dev.KG0) * 4};
-  size_t off[13], tot = 0;
-  for (int i = 0; i < 13; ++i) { off[i] = tot; tot += (sz[i] + 255) & ~(size_t)255; }
-  if (hipMalloc(&h->mem, tot) != hipSuccess) { delete h; return fail("mopo_rollout_create: out of device memory"); }
+  size_t off[13];
+  if (hipMalloc(&h->mem, carve(sz, 13, off)) != hipSuccess) { delete h; return fail("mopo_rollout_create: out of device memory"); }
   char* m = (char*)h->mem;
   h->obs[0] = (double*)(m + off[0]); h->obs[1] = (double*)(m + off[1]);
   h->uid[0] = (int64_t*)(m + off[2]); h->uid[1] = (int64_t*)(m + off[3]);

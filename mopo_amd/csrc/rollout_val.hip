@@ -9,16 +9,14 @@
 //   (rollout_xs_wide         wide models only: the scaled input rows; narrow models hand the ensemble the
 //                            raw f64 obs / f32 act view, FwdArgs::xs = NULL)
 //   bnn_fwd ROLLOUT          the ensemble, as in the training rollout
-//   rollout_val_post         FakeEnv's sample / penalty / termination of rollout_post_kernel, then the errors
+//   rollout_val_post         FakeEnv's sample / penalty / termination (rollout_post.h), then the errors
 //                            against pool row start + k and the continuation test on the DATA (terminal flag,
 //                            end of pool, obs[j + 1] == next_obs[j] bit for bit)
 //   rollout_compact          obs = next_obs[continues]
 //   rollout_eval_advance     live count <- survivors
 // then rollout_val_stats reduces the [K][B] tables to the per-step and pooled statistics.
 #include "penalty.h"
-#include "rollout.h"
-
-#include <cstdlib>
+#include "rollout_post.h"
 
 namespace mopo {
 
@@ -119,66 +117,22 @@ struct ValPostArgs {
   ValTabs t;
 };
 
-// One FakeEnv step for VAL_RPB rows per block in rollout_eval_post_kernel's form (a 32-lane group per row,
-// a lane per output dim; same f32 residual add, f64 sample, Philox counters, both penalty kinds,
-// deterministic mean over all members), then against pool row j = start + k: the errors in f64, the
-// termination rule's verdict beside the data's flag, and whether the segment goes on.  A live row is the only
-// row of its segment, so the segment's outputs take plain stores.
-constexpr int VAL_RPB = 8;   // PB % VAL_RPB == 0: a block's rows share one compaction chunk
+// One FakeEnv step (rollout_post.h) for POST_RPB rows per block, a 32-lane group per row.  Its own part,
+// against pool row j = start + k: the errors in f64, the termination rule's verdict beside the data's flag, and
+// whether the segment goes on.  A live row is the only row of its segment, so the segment's outputs take plain
+// stores.
 __global__ __launch_bounds__(256) void rollout_val_post_kernel(const ValPostArgs va) {
   const PostArgs& a = va.p;
-  __shared__ double srow[VAL_RPB][33];
-  __shared__ int kept[VAL_RPB];
+  __shared__ double srow[POST_RPB][33];
+  __shared__ int kept[POST_RPB];
   const int tid = threadIdx.x, sub = tid & 31, rl = tid >> 5;
-  const int64_t row = (int64_t)blockIdx.x * VAL_RPB + rl;
+  const int64_t row = (int64_t)blockIdx.x * POST_RPB + rl;
   const int O = a.O, D = O + 1;
   const int64_t count = *a.cnt;
   const bool live = row < count;
   const bool on = live && sub < D;
-  double s = 0.0;
-  // member e's mean of this lane's dim after the residual add, in f32 (fake_env.py:66)
-  const double ob = on && sub >= 1 ? a.obs[row * O + sub - 1] : 0.0;
-  auto member_mean = [&](int e) {
-    const float m = a.mean_all[((int64_t)e * a.all_stride + row) * D + sub];
-    return sub >= 1 ? (float)((double)m + ob) : m;
-  };
-  float pen_d = 0.f;
-  if (a.pen_dist) {  // max_e || mean_e - mean_e' mean_e' || over the obs dims (fake_env.py:98-108)
-    float sum = 0.f;
-    if (on && sub >= 1)
-      for (int e = 0; e < a.E; ++e) sum += member_mean(e);
-    const float avg = sum / (float)a.E;
-    for (int e = 0; e < a.E; ++e) {
-      const float dd = on && sub >= 1 ? member_mean(e) - avg : 0.f;
-      float q = dd * dd;
-#pragma unroll
-      for (int o = 16; o >= 1; o >>= 1) q += __shfl_xor(q, o);       // the row's 32-lane group
-      pen_d = fmaxf(pen_d, sqrtf(q));
-    }
-  }
-  if (on && a.det) {  // samples = mean over ALL members of the means (fake_env.py:69-70, 84-86)
-    float acc = 0.f;
-    for (int e = 0; e < a.E; ++e) acc += member_mean(e);
-    s = (double)(acc / (float)a.E);
-    srow[rl][sub] = s;
-  } else if (on) {
-    float m = a.mean_sel[row * D + sub];
-    if (sub >= 1) m = (float)((double)m + ob);                      // fake_env.py:66
-    double e;
-    if (a.eps) {
-      e = a.eps[row * D + sub];
-    } else {  // Philox normal `sub` of the row's stream (perf mode of fake_env.py:72)
-      const int64_t u = a.uid[row];
-      u32x4 c{(uint32_t)u, (uint32_t)((uint64_t)u >> 32) ^ ((uint32_t)(sub >> 2) << 20), a.step, RNG_OBS_NOISE};
-      u32x4 r = philox(c, (uint32_t)a.seed, (uint32_t)(a.seed >> 32));
-      float z0, z1;
-      if (sub & 2) box_muller(r.z, r.w, z0, z1);
-      else box_muller(r.x, r.y, z0, z1);
-      e = (double)((sub & 1) ? z1 : z0);
-    }
-    s = (double)m + e * (double)a.std_sel[row * D + sub];          // fake_env.py:72
-    srow[rl][sub] = s;
-  }
+  float pen_d;
+  const double s = post_group_step(a, row, sub, on, srow[rl], pen_d);
   __syncthreads();
   if (on && sub >= 1) a.obs_next[row * O + sub - 1] = s;           // next_obs = samples[:, 1:] (:90)
 
@@ -205,16 +159,15 @@ __global__ __launch_bounds__(256) void rollout_val_post_kernel(const ValPostArgs
   if (sub == 0) {
     bool keep = false;
     if (inside) {
-      const bool term = term_fn(a.term_kind, &srow[rl][1], O);     // fake_env.py:91
-      const float pen = a.pen_dist ? pen_d : __uint_as_float(a.pen[row]);
+      const PostVerdict v = post_verdict(a, row, srow[rl], s, pen_d);   // its penalized reward is not used
       const double er = s - (double)a.pool.d_rew[j];               // unpenalized reward (fake_env.py:89)
       const uint8_t td = a.pool.d_term[j] ? 1 : 0;
       const int64_t at = (int64_t)va.k * va.B + seg;
       va.t.err[at] = sqrt(q + er * er);
       va.t.err_obs[at] = sqrt(q);
       va.t.err_rew[at] = er;
-      va.t.pen[at] = pen;
-      va.t.term_pred[at] = term ? 1 : 0;
+      va.t.pen[at] = v.pen;
+      va.t.term_pred[at] = v.term ? 1 : 0;
       va.t.term_data[at] = td;
       va.t.len[seg] = va.k + 1;
       int end = 0;
@@ -229,13 +182,7 @@ __global__ __launch_bounds__(256) void rollout_val_post_kernel(const ValPostArgs
     if (live) a.keep[row] = keep ? 1 : 0;
     kept[rl] = keep ? 1 : 0;
   }
-  __syncthreads();
-  if (tid == 0) {
-    int t = 0;
-#pragma unroll
-    for (int i = 0; i < VAL_RPB; ++i) t += kept[i];
-    if (t) atomicAdd(a.blockcnt + (int64_t)blockIdx.x * VAL_RPB / PB, t);
-  }
+  post_count_kept<POST_RPB>(kept, a.blockcnt, (int64_t)blockIdx.x * POST_RPB);
 }
 
 // The statistics, one 256-thread workgroup per row of the table (rollout_eval_stats_kernel's scheme): row
@@ -312,13 +259,6 @@ __global__ __launch_bounds__(VST) void rollout_val_stats_kernel(ValTabs t, int64
   }
 }
 
-// MOPO_EVAL_POLL, as the evaluation reads it: steps between two read-backs of the live count (0: never)
-static int val_poll() {
-  const char* e = std::getenv("MOPO_EVAL_POLL");
-  const int n = e ? std::atoi(e) : 32;
-  return n < 0 ? 0 : n;
-}
-
 }  // namespace mopo
 
 using namespace mopo;
@@ -327,42 +267,34 @@ extern "C" int mopo_rollout_validate(mopo_rollout_t hh, const mopo_rollout_args*
                                      const mopo_val_args* v, void* stream) {
   Rollout* h = reinterpret_cast<Rollout*>(hh);
   MOPO_REQUIRE(h && a && pool && v, "mopo_rollout_validate: NULL argument");
-  MOPO_REQUIRE(a->B >= 0 && a->B <= h->Bmax, "mopo_rollout_validate: B exceeds the handle's max_batch");
+  if (rollout_check_args(h, a, "mopo_rollout_validate", false)) return -1;
   MOPO_REQUIRE(a->horizon >= 1 && a->horizon <= 4095,
                "mopo_rollout_validate: the segment length K must be in [1, 4095] (the Philox step key is "
                "epoch * 4096 + 1 + step)");
-  MOPO_REQUIRE(a->term_kind >= 0 && a->term_kind < MOPO_TERM_KINDS, "mopo_rollout_validate: unknown term_kind");
-  MOPO_REQUIRE(a->penalty_learned_var >= 0 && a->penalty_learned_var < MOPO_PENALTY_KINDS,
-               std::string("mopo_rollout_validate") + kPenaltyKindMsg);
-  MOPO_REQUIRE(a->deterministic || a->d_model_inds || (a->d_elites && a->n_elites > 0),
-               "mopo_rollout_validate: elites required");
   MOPO_REQUIRE(pool->d_obs && pool->d_act && pool->d_rew && pool->d_term && pool->d_next_obs && pool->d_state &&
                    pool->max_size >= 1,
                "mopo_rollout_validate: NULL pool field");
   if (a->B == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   Bnn* bnn = h->bnn;
-  const int O = bnn->O, A = bnn->A, D = O + 1, K = a->horizon;
+  const int A = bnn->A, K = a->horizon;
   const int64_t B = a->B;
-  const int nblk = ceil_div((int)B, PB);
   const uint32_t step0 = a->epoch * 4096u;
 
   if (!h->val_mem) {
-    const size_t n = ((size_t)h->Bmax * 8 + 255) & ~(size_t)255;
-    MOPO_HIP(hipMalloc(&h->val_mem, 2 * n));
+    const size_t sz[] = {(size_t)h->Bmax * 8, (size_t)h->Bmax * 8};
+    size_t off[2];
+    MOPO_HIP(hipMalloc(&h->val_mem, carve(sz, 2, off)));
     h->val_start = (int64_t*)h->val_mem;
-    h->val_gidx = (int64_t*)((char*)h->val_mem + n);
+    h->val_gidx = (int64_t*)((char*)h->val_mem + off[1]);
   }
   // the tables the caller did not ask for live in the handle (the statistics are reduced from them)
   const size_t kb = (size_t)K * B;
   void* const given[] = {v->d_err, v->d_err_obs, v->d_err_rew, v->d_pen, v->d_term_pred, v->d_term_data,
                          v->d_length, v->d_end, v->d_stats};
   const size_t sz[] = {kb * 8, kb * 8, kb * 8, kb * 4, kb, kb, (size_t)B * 4, (size_t)B, (size_t)(K + 1) * 16 * 8};
-  size_t off[9], tot = 0;
-  for (int i = 0; i < 9; ++i) {
-    off[i] = tot;
-    if (!given[i]) tot += (sz[i] + 255) & ~(size_t)255;
-  }
+  size_t off[9];
+  const size_t tot = carve(sz, 9, off, given);
   if (tot > h->val_tab_bytes) {
     if (h->val_tab) (void)hipFree(h->val_tab);
     h->val_tab = nullptr;
@@ -376,81 +308,53 @@ extern "C" int mopo_rollout_validate(mopo_rollout_t hh, const mopo_rollout_args*
             (int32_t*)p[6], (uint8_t*)p[7]};
   double* stats = (double*)p[8];
 
-  const bool det = a->deterministic != 0;
-  const bool pen_dist = a->penalty_learned_var == 0;   // the penalty is always computed
-  // kinds >= 2 (penalty.hip): every member's mean and std, reduced by one kernel behind the ensemble
-  const int pen_kind = a->penalty_learned_var >= MOPO_PENALTY_MAX_PAIRWISE ? a->penalty_learned_var : 0;
+  StepModes m;
+  if (rollout_modes(h, a, true, &m)) return -1;   // the penalty is always computed
   // the error the penalty is compared with: err_obs for the kinds over the observation outputs (0 and 2)
-  const bool over_obs = pen_dist || pen_kind == MOPO_PENALTY_MAX_PAIRWISE;
-  const bool need_all = det || pen_dist || pen_kind;
-  if (need_all && !h->mean_all)
-    MOPO_HIP(hipMalloc(&h->mean_all, (size_t)bnn->E * h->Bmax * D * sizeof(float)));
-  if (pen_kind && rollout_penalty_alloc(h)) return -1;
+  const bool over_obs = m.pen_dist || m.pen_kind == MOPO_PENALTY_MAX_PAIRWISE;
 
   h->next_step = 0;   // a staged step range must not continue across a validation
   hipLaunchKernelGGL(rollout_val_init_kernel, dim3((unsigned)((kb + 255) / 256)), dim3(256), 0, s, B, K, t, *pool,
                      a->d_start_idx, a->seed, step0, a->uid_offset, h->val_start, h->val_gidx, v->d_start);
   MOPO_HIP(hipGetLastError());
   // the start states obs[r_b] in f64, the row ids and the live count, from the rows the init kernel chose
-  hipLaunchKernelGGL(rollout_start_kernel, dim3((unsigned)((B + START_ROWS - 1) / START_ROWS)), dim3(START_TPB), 0, s,
-                     pool->d_obs, pool->max_size, h->val_gidx, O, B, a->seed, step0, a->uid_offset, h->obs[0],
-                     h->uid[0], h->cnt, 1, B);
-  MOPO_HIP(hipGetLastError());
+  if (rollout_start(h, a, pool->d_obs, pool->max_size, h->val_gidx, 1, B, s)) return -1;
 
   const bool wide = bnn->dev.KG0 > 2;   // internal.h bnn_wide: 64-slot xs rows
   int uc = 0;
   const int oc = 0;                     // every step compacts obs[1] back into obs[0]
-  const int poll = val_poll();
+  const int poll = rollout_poll_steps();
   for (int i = 0; i < K; ++i) {
-    const uint32_t st = step0 + 1 + i;
     ValGatherArgs ga{};
     ga.cnt = h->cnt; ga.uid = h->uid[uc]; ga.uid_offset = a->uid_offset; ga.start = h->val_start;
     ga.k = i; ga.A = A; ga.pool = *pool; ga.act = h->act; ga.pen_zero = h->pen;
-    ga.sel_out = det ? nullptr : h->sel;
+    ga.sel_out = m.det ? nullptr : h->sel;
     ga.sel_in = a->d_model_inds ? a->d_model_inds + (int64_t)i * B : nullptr;
-    ga.elites = a->d_elites; ga.n_elites = a->n_elites; ga.seed = a->seed; ga.step = st;
+    ga.elites = a->d_elites; ga.n_elites = a->n_elites; ga.seed = a->seed; ga.step = step0 + 1 + i;
     hipLaunchKernelGGL(rollout_val_gather_kernel, dim3((unsigned)((B * 8 + 255) / 256)), dim3(256), 0, s, ga);
     MOPO_HIP(hipGetLastError());
-    if (wide) {
-      hipLaunchKernelGGL(rollout_xs_wide_kernel, dim3(ceil_div((int)B, 16)), dim3(256), 0, s, h->obs[oc], h->act, O, A,
-                         bnn->dev.mu, bnn->dev.sigma, B, h->cnt, h->xs);
-      MOPO_HIP(hipGetLastError());
-    }
+    if (wide && rollout_xs_wide(h, oc, 0, B, h->cnt, h->xs, s)) return -1;
 
-    FwdArgs f{};
-    f.in = FwdIn{h->obs[oc], 1, O, h->act, 0, A};
-    f.B = B; f.d_count = h->cnt; f.xs = wide ? h->xs : nullptr;
-    f.pen_bits = h->pen; f.sel = det ? nullptr : h->sel; f.mean_sel = h->mean_sel; f.std_sel = h->std_sel;
-    f.mean_all = need_all ? h->mean_all : nullptr;
-    f.std_all = pen_kind ? h->std_all : nullptr;
-    f.all_stride = h->Bmax;
+    const FwdArgs f = rollout_fwd_args(h, m, oc, 0, B, h->cnt, wide ? h->xs : nullptr);
     if (launch_bnn_fwd(bnn, FWD_ROLLOUT, f, s)) return -1;
-    if (pen_kind && rollout_penalty(h, pen_kind, 0, B, h->cnt, s)) return -1;
+    if (m.pen_kind && rollout_penalty(h, m.pen_kind, 0, B, h->cnt, s)) return -1;
 
     ValPostArgs va{};
-    PostArgs& pa = va.p;
-    pa.O = O; pa.cnt = h->cnt; pa.obs = h->obs[oc]; pa.uid = h->uid[uc];
-    pa.mean_sel = h->mean_sel; pa.std_sel = h->std_sel; pa.pen = h->pen;
-    pa.eps = a->d_eps_obs ? a->d_eps_obs + (int64_t)i * B * D : nullptr;
-    pa.seed = a->seed; pa.step = st; pa.term_kind = a->term_kind;
-    pa.obs_next = h->obs[oc ^ 1]; pa.keep = h->keep; pa.blockcnt = h->blockcnt;
-    pa.pool = *pool; pa.stage_base = -1;
-    pa.mean_all = f.mean_all; pa.E = bnn->E; pa.all_stride = h->Bmax; pa.pen_dist = pen_dist; pa.det = det;
+    va.p = rollout_post_args(h, a, m, i, oc, uc, 0, h->cnt, true);
+    va.p.pool = *pool;
     va.uid_offset = a->uid_offset; va.B = B; va.start = h->val_start; va.k = i; va.K = K; va.t = t;
-    MOPO_HIP(hipMemsetAsync(h->blockcnt, 0, (size_t)nblk * sizeof(int), s));
-    hipLaunchKernelGGL(rollout_val_post_kernel, dim3(ceil_div((int)B, VAL_RPB)), dim3(256), 0, s, va);
+    if (rollout_zero_chunks(h, B, s)) return -1;
+    hipLaunchKernelGGL(rollout_val_post_kernel, dim3(ceil_div((int)B, POST_RPB)), dim3(256), 0, s, va);
     MOPO_HIP(hipGetLastError());
-    hipLaunchKernelGGL(rollout_compact_kernel, dim3(nblk), dim3(PB), 0, s, O, h->blockcnt, h->keep, h->cnt,
-                       h->obs[oc ^ 1], h->obs[oc], h->uid[uc], h->uid[uc ^ 1], h->cnt + 1);
+    if (rollout_compact(h, B, oc, uc, s)) return -1;
     hipLaunchKernelGGL(rollout_eval_advance_kernel, dim3(1), dim3(1), 0, s, h->cnt, (int64_t*)nullptr, i);
     uc ^= 1;
     MOPO_HIP(hipGetLastError());
     // once no segment is alive the remaining steps would all return on the zero count: skip them
     if (poll > 0 && (i + 1) % poll == 0 && i + 1 < K) {
-      int live = 0;
-      MOPO_HIP(hipMemcpyAsync(&live, h->cnt, sizeof(int), hipMemcpyDeviceToHost, s));
-      MOPO_HIP(hipStreamSynchronize(s));
-      if (live == 0) break;
+      bool none;
+      if (rollout_none_alive(h, s, &none)) return -1;
+      if (none) break;
     }
   }
   hipLaunchKernelGGL(rollout_val_stats_kernel, dim3(K + 1), dim3(VST), 0, s, t, B, K, over_obs ? 1 : 0, stats,

@@ -6,7 +6,7 @@ The reference draws every rollout random number from numpy's global MT19937 (sta
 member choice ``bnn.py:343``); parity mode injects exactly those draws.  Perf mode replaces them with
 counter-based Philox4x32-10 streams keyed by the global row id, so that any row can be recomputed
 on its own.  This module restates those device streams (``mopo_amd/csrc/common.h`` philox /
-box_muller, ``rollout.hip`` rollout_start_kernel and rollout_post_kernel, ``actor.hip``
+box_muller, ``rollout.hip`` rollout_start_kernel, ``rollout_post.h`` post_obs_noise, ``actor.hip``
 actor_noise and the member choice) so that sampled rows of a full-size perf-mode rollout can be
 checked against the oracle.  Philox itself is pinned by the Random123 known-answer vectors
 (tests/test_oracle.py); the streams' layout is pinned by the GPU test that replays them.
@@ -78,7 +78,7 @@ def act_noise(uid, seed, step, A):
 
 
 def obs_noise(uid, seed, step, D):
-    """rollout_post_kernel: the observation-noise normal per output dim (fake_env.py:72)."""
+    """rollout_post.h post_obs_noise: the observation-noise normal per output dim (fake_env.py:72)."""
     return _normals(uid, seed, step, RNG_OBS_NOISE, D)
 
 
