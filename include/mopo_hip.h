@@ -59,10 +59,21 @@ typedef struct mopo_bnn_s* mopo_bnn_t;
  * width.  385..400 runs in fp32 and f16x3; 257..384 and above 400 are refused here.  fp32, bf16x6 (up to 256)
  * and f16x3 run every form; bf16 and bf16x3 keep the widths they had (up to 64, 193..208, 385..416).
  * Up to 32 inputs and obs_dim <= 23 (one or two 16-wide input k-groups, at most 48 head slots) every dtype
- * runs.  Wider models (e.g. ant's 27 + 8) run one padded form, 64 input slots and 64 head slots: fp32 at
+ * runs, from obs_dim = act_dim = 1 on.  The fused [mean | log-var] head needs ceil(2 D / 16) blocks of 16 slots;
+ * the kernels exist for 2 and 3 blocks (16-bit dtypes at hidden <= 32 and 385..416: 3 only), so a smaller head
+ * runs on the smallest count its (dtype, hidden form) has, the spare slots holding zero weights and storing
+ * nothing (pendulum's 3 + 1 on 2 blocks; hopper's 11 + 3 at hidden 32 in a 16-bit dtype on 3).
+ * Wider models (e.g. ant's 27 + 8) run one padded form, 64 input slots and 64 head slots: fp32 at
  * every hidden size above, bf16x6 and f16x3 up to hidden 208 (so e.g. hidden 256 or 400 with a 16-bit dtype,
- * and bf16 / bf16x3 at any width, are refused here on a wide shape, with a message naming what runs). */
+ * and bf16 / bf16x3 at any width, are refused here on a wide shape, with a message naming what runs).
+ * A handle that create returns has its kernel: mopo_bnn_predict, mopo_fakeenv_step and the ensemble launches of the
+ * rollouts never refuse it for its shape (the rollouts' policy has limits of its own: act_dim <= 8). */
 int mopo_bnn_create(mopo_bnn_t* out, int E, int obs_dim, int act_dim, int hidden, int smv, int dtype);
+/* Host only (no device call): the forward form that runs a shape.  Returns 1 where a kernel runs it and writes
+ * the layer-0 k-groups of 16 inputs, the hidden blocks of the form, the head blocks and wide (0 / 1) to blocks4
+ * (may be NULL); 0 where no kernel does, which is exactly where mopo_bnn_create refuses.  mopo_bnn_create builds
+ * its handle from the same answer. */
+int mopo_bnn_forward_form(int obs_dim, int act_dim, int hidden, int dtype, int* blocks4);
 /* Host only: the hidden width the device form runs for a logical width (wide: obs_dim + act_dim > 32 or
  * obs_dim > 23), or -1 where mopo_bnn_create refuses.  >= hidden, monotone in hidden, and hidden itself for
  * every width that has a form of its own (32, 64, 128, 193..208, 256, 400). */
@@ -86,7 +97,8 @@ int mopo_bnn_packed_copy(mopo_bnn_t h, int to_handle, void* d_buf, int64_t nbyte
 
 /* ---- FakeEnv.step ------------------------------------------------------------------- */
 /* termination rules of mopo/static/<domain>.py: NONE covers halfcheetah{,jump,vel,veljump}, point2denv,
- * point2dwallenv and pendulum (never done); ANT covers ant.py / antangle.py; HUMANOID humanoid.py */
+ * point2dwallenv and pendulum (never done); ANT covers ant.py / antangle.py; HUMANOID humanoid.py.  WALKER2D and
+ * HOPPER read observations 0 and 1: mopo_fakeenv_step and the rollouts refuse them on a model with obs_dim 1. */
 enum { MOPO_TERM_NONE = 0, MOPO_TERM_HALFCHEETAH = 0, MOPO_TERM_WALKER2D = 1, MOPO_TERM_HOPPER = 2,
        MOPO_TERM_ANT = 3, MOPO_TERM_HUMANOID = 4, MOPO_TERM_KINDS = 5 };
 

@@ -59,6 +59,7 @@ SIGNATURES = {
     'mopo_bnn_set_params': (c_int, [c_void_p, C.POINTER(c_void_p), c_int]),
     'mopo_actor_device_hidden': (c_int, [c_int, c_int]),
     'mopo_bnn_device_hidden': (c_int, [c_int, c_int, c_int]),
+    'mopo_bnn_forward_form': (c_int, [c_int, c_int, c_int, c_int, C.POINTER(c_int)]),
     'mopo_bnn_predict': (c_int, [c_void_p, c_void_p, c_int, c_i64, c_void_p, c_void_p, c_void_p]),
     'mopo_bnn_packed_bytes': (c_i64, [c_void_p]),
     'mopo_bnn_packed_copy': (c_int, [c_void_p, c_int, c_void_p, c_i64, c_void_p]),

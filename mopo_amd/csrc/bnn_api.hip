@@ -16,53 +16,34 @@ extern "C" int mopo_bnn_create(mopo_bnn_t* out, int E, int obs_dim, int act_dim,
                                int dtype) {
   MOPO_REQUIRE(out != nullptr, "mopo_bnn_create: out is NULL");
   MOPO_REQUIRE(E >= 1 && E <= 256, "mopo_bnn_create: num_networks must be in [1, 256]");
-  MOPO_REQUIRE(obs_dim >= 1 && act_dim >= 1, "mopo_bnn_create: bad obs/act dims");
-  MOPO_REQUIRE(dtype >= 0 && dtype <= 4,
-               "mopo_bnn_create: dtype must be 0 (fp32), 1 (bf16), 2 (bf16x3), 3 (bf16x6) or 4 (f16x3)");
+  // the form that runs this shape (internal.h bnn_forward_form, the one statement of it): input k-groups, the
+  // hidden form -- its own where the width has one, else the smallest that holds it -- and the head blocks; the
+  // packers fill the form's spare units and head slots with zeros.  A shape no kernel runs is refused here.
+  BnnForm f;
+  if (const char* why = bnn_forward_form(obs_dim, act_dim, hidden, dtype, &f)) {
+    return fail(std::string("mopo_bnn_create: ") + why + " (got obs_dim " + std::to_string(obs_dim) + ", act_dim " +
+                std::to_string(act_dim) + ", hidden " + std::to_string(hidden) + ", dtype " + std::to_string(dtype) +
+                ")");
+  }
   auto h = std::make_unique<Bnn>();   // released to the caller only once every check has passed
   h->E = E; h->O = obs_dim; h->A = act_dim; h->H = hidden; h->smv = smv; h->dtype = dtype;
   BnnDev& d = h->dev;
   d.E = E; d.O = obs_dim; d.A = act_dim; d.IN = obs_dim + act_dim; d.H = hidden; d.D = obs_dim + 1;
-  if (d.IN > 16 * MAX_IN_KG || d.D > 32) {
-    return fail("mopo_bnn_create: obs_dim + act_dim must be <= 64 and obs_dim <= 31 (got obs_dim " +
-                std::to_string(obs_dim) + ", act_dim " + std::to_string(act_dim) + ")");
-  }
-  // wide models (more than 32 inputs or more than 3 head blocks) run one padded form: 4 input k-groups, 4 head blocks
-  const bool wide = bnn_wide(d.IN, d.D);
-  d.KG0 = wide ? MAX_IN_KG : ceil_div(d.IN, 16);
-  d.NBH = ceil_div(hidden, 16);
-  d.NBO = wide ? 4 : ceil_div(2 * d.D, 16);
-  d.NB2 = (d.NBH + 1) / 2 * 2;
-  d.BS = d.NB2 * 16;
-  if (wide && dtype != DT_FP32 &&
-      !((dtype == DT_BF16X6 || dtype == DT_F16X3) && d.NBH <= 13)) {   // every width up to 208 has a 16-bit ring form
-    return fail(std::string("mopo_bnn_create: ") + kWide16Msg);
-  }
-  // the 16-bit kernels' NB2 = 14 shape is H = 200's 13 blocks: bf16x6 / f16x3 run 209..224 on 16 blocks
-  if ((dtype == DT_BF16 || dtype == DT_BF16X3) && d.NB2 == 14 && d.NBH != 13) {
-    return fail("mopo_bnn_create: bf16 and bf16x3 do not support hidden sizes 209..224 (got " +
-                std::to_string(hidden) + "; use fp32, bf16x6 or f16x3)");
-  }
-  if (dtype == 3 && d.NB2 > 16) {   // launch_bf16_t: no bf16x6 kernel above H = 256
-    return fail("mopo_bnn_create: bf16x6 supports hidden sizes <= 256 (use f16x3 or fp32)");
-  }
-  // the form that runs this width (internal.h bnn_form_blocks): its own where it has one, else the smallest that
-  // holds it; the packer fills the form's spare units with zeros
-  const int form = bnn_form_blocks(hidden, dtype, wide);
-  if (form < 0) {
-    if (dtype == DT_BF16 || dtype == DT_BF16X3)
-      return fail("mopo_bnn_create: bf16 and bf16x3 run hidden sizes up to 64, 193..208 and 385..416 only (got " +
-                  std::to_string(hidden) + "; fp32, bf16x6 and f16x3 run every hidden size up to 256)");
-    return fail("mopo_bnn_create: no kernel for hidden size " + std::to_string(hidden) +
-                " (every hidden size up to 256 runs in fp32, bf16x6 and f16x3, 385..400 in fp32 and f16x3; a wide "
-                "model's bf16x6 / f16x3 stop at 208)");
-  }
-  h->HD = bnn_device_hidden(hidden, dtype, wide);
-  d.NBH = form;
+  d.KG0 = f.KG0;
+  d.NBH = f.NBH;
+  d.NBO = f.NBO;
+  h->HD = f.HD;
   d.NB2 = (d.NBH + 1) / 2 * 2;
   d.BS = d.NB2 * 16;
   *out = reinterpret_cast<mopo_bnn_t>(h.release());
   return 0;
+}
+
+extern "C" int mopo_bnn_forward_form(int obs_dim, int act_dim, int hidden, int dtype, int* blocks4) {
+  BnnForm f;
+  if (bnn_forward_form(obs_dim, act_dim, hidden, dtype, &f)) return 0;
+  if (blocks4) { blocks4[0] = f.KG0; blocks4[1] = f.NBH; blocks4[2] = f.NBO; blocks4[3] = f.wide; }
+  return 1;
 }
 
 extern "C" int mopo_bnn_device_hidden(int hidden, int dtype, int wide) {

@@ -135,6 +135,9 @@ extern "C" int mopo_fakeenv_step(mopo_bnn_t hh, const mopo_fakeenv_args* a, void
   MOPO_REQUIRE(h->O + 1 <= MAXD, "mopo_fakeenv_step: obs_dim too large");
   MOPO_REQUIRE(a->B >= 0, "mopo_fakeenv_step: negative batch");
   MOPO_REQUIRE(a->term_kind >= 0 && a->term_kind < MOPO_TERM_KINDS, "mopo_fakeenv_step: unknown term_kind");
+  MOPO_REQUIRE(h->O >= 2 || (a->term_kind != MOPO_TERM_WALKER2D && a->term_kind != MOPO_TERM_HOPPER),
+               "mopo_fakeenv_step: the walker2d and hopper termination rules read observations 0 and 1 (obs_dim must "
+               "be >= 2)");
   MOPO_REQUIRE(a->penalty_learned_var >= 0 && a->penalty_learned_var < MOPO_PENALTY_KINDS,
                std::string("mopo_fakeenv_step") + kPenaltyKindMsg);
   if (a->B == 0) return 0;  // empty batch: nothing to read or write (empty buffers may be NULL)

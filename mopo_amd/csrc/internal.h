@@ -96,6 +96,67 @@ static const char* const kWidths16Msg =
     "bnn: hidden sizes 65..128 and 209..256 run in fp32, bf16x6 and f16x3 (a wide model -- obs_dim + act_dim > 32 or "
     "obs_dim > 23 -- in fp32, and up to 128 in bf16x6 / f16x3); bf16 and bf16x3 are not supported there";
 
+// ---- which forward form runs a shape ---------------------------------------------------------------------------
+// The head kernels that exist for a narrow shape (at most 32 inputs, obs_dim <= 23), per dtype class and hidden
+// form: fp32 has head-block counts NBO = 2 and 3 at every form; the 16-bit kernels 2 and 3 at 4, 8, 13 and 16
+// hidden blocks (NB2 = 4, 8, 14, 16) and 3 alone at 1..2 and 25..26 (NB2 = 2, 26).  No form has a 1-block head.
+// This is the table launch_bnn_fwd's arms (bnn.hip, bnn_widths.hip, bnn_widths16.hip) spell out as template
+// arguments; a handle whose NBO came from bnn_forward_form always finds its arm.
+inline bool bnn_head_kernel(int dtype, int nb2, int nbo) {
+  if (nbo == 3) return true;
+  if (nbo != 2) return false;
+  return dtype == 0 || (nb2 != 2 && nb2 != 26);
+}
+
+// The form of a handle: layer-0 k-groups, hidden blocks, head blocks, wide (bnn_wide), device hidden width.
+struct BnnForm {
+  int KG0, NBH, NBO, wide, HD;
+};
+
+// THE statement of which forward kernel runs (obs_dim, act_dim, hidden, dtype): fills *f and returns nullptr, or
+// returns the limit the shape breaks (no kernel runs it).  mopo_bnn_create builds its handle from this answer and
+// the export mopo_bnn_forward_form gives it to callers; the launch dispatch only reads the handle.
+// The head takes the smallest block count >= ceil(2 D / 16) that the (dtype, hidden form) has a kernel for:
+// head_col leaves the slots beyond 2 D empty, the packers turn them into zero weights, and the head epilogue
+// works from D alone, so the spare blocks compute and store nothing.
+inline const char* bnn_forward_form(int obs_dim, int act_dim, int hidden, int dtype, BnnForm* f) {
+  if (obs_dim < 1 || act_dim < 1) return "bad obs/act dims (both must be >= 1)";
+  if (dtype < 0 || dtype > 4) return "dtype must be 0 (fp32), 1 (bf16), 2 (bf16x3), 3 (bf16x6) or 4 (f16x3)";
+  const int IN = obs_dim + act_dim, D = obs_dim + 1;
+  if (IN > 16 * MAX_IN_KG || D > 32) return "obs_dim + act_dim must be <= 64 and obs_dim <= 31";
+  const bool wide = bnn_wide(IN, D);
+  const bool split = dtype == DT_BF16X6 || dtype == DT_F16X3;
+  const int nb = (hidden + 15) / 16, nb2 = (nb + 1) / 2 * 2;
+  // every width up to 208 has a wide 16-bit ring form
+  if (wide && dtype != DT_FP32 && !(split && nb <= 13))
+    return kWide16Msg;
+  // the 16-bit kernels' NB2 = 14 shape is H = 200's 13 blocks: bf16x6 / f16x3 run 209..224 on 16 blocks
+  if ((dtype == DT_BF16 || dtype == DT_BF16X3) && nb2 == 14 && nb != 13)
+    return "bf16 and bf16x3 do not support hidden sizes 209..224 (use fp32, bf16x6 or f16x3)";
+  if (dtype == DT_BF16X6 && nb2 > 16)   // launch_bf16_t: no bf16x6 kernel above H = 256
+    return "bf16x6 supports hidden sizes <= 256 (use f16x3 or fp32)";
+  const int form = bnn_form_blocks(hidden, dtype, wide);
+  if (form < 0) {
+    if (dtype == DT_BF16 || dtype == DT_BF16X3)
+      return "bf16 and bf16x3 run hidden sizes up to 64, 193..208 and 385..416 only (fp32, bf16x6 and f16x3 run "
+             "every hidden size up to 256)";
+    return "no kernel for this hidden size (every hidden size up to 256 runs in fp32, bf16x6 and f16x3, 385..400 in "
+           "fp32 and f16x3; a wide model's bf16x6 / f16x3 stop at 208)";
+  }
+  BnnForm r;
+  r.wide = wide ? 1 : 0;
+  r.KG0 = wide ? MAX_IN_KG : (IN + 15) / 16;
+  r.NBH = form;
+  r.HD = bnn_device_hidden(hidden, dtype, wide);
+  r.NBO = wide ? 4 : (2 * D + 15) / 16;
+  if (!wide) {
+    const int fb2 = (form + 1) / 2 * 2;
+    while (r.NBO < 3 && !bnn_head_kernel(dtype, fb2, r.NBO)) ++r.NBO;
+  }
+  if (f) *f = r;
+  return nullptr;
+}
+
 struct Bnn {
   int E, O, A, H, smv, dtype;
   int HD = 0;  // bnn_device_hidden(H): the width the tail-skipping and packed-remainder choices are made from

@@ -272,6 +272,8 @@ int rollout_check_args(const Rollout* h, const mopo_rollout_args* a, const char*
   const std::string w(who);
   MOPO_REQUIRE(a->B >= 0 && a->B <= h->Bmax, w + ": B exceeds the handle's max_batch");
   MOPO_REQUIRE(a->term_kind >= 0 && a->term_kind < MOPO_TERM_KINDS, w + ": unknown term_kind");
+  MOPO_REQUIRE(h->bnn->O >= 2 || (a->term_kind != MOPO_TERM_WALKER2D && a->term_kind != MOPO_TERM_HOPPER),
+               w + ": the walker2d and hopper termination rules read observations 0 and 1 (obs_dim must be >= 2)");
   MOPO_REQUIRE(a->penalty_learned_var >= 0 && a->penalty_learned_var < MOPO_PENALTY_KINDS, w + kPenaltyKindMsg);
   MOPO_REQUIRE((!policy && a->deterministic) || a->d_model_inds || (a->d_elites && a->n_elites > 0),
                w + ": elites required");

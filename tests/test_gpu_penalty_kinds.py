@@ -74,27 +74,27 @@ def _c_penalty(params, obs, act, kind):
 @pytest.mark.parametrize('OA', pk.KERNEL_OA, ids=lambda oa: 'O%d' % oa[0])
 @pytest.mark.parametrize('E', pk.KERNEL_E)
 def test_kernel_against_f64_on_the_device_outputs(E, OA, smv):
-    """Through mopo_fakeenv_step on the device's own member outputs.  The ensemble kernels run D >= 9 only (two
-    head blocks at least: mopo_bnn_predict refuses D = 4), so at (3, 1) the member outputs are the oracle's f32
-    forward of the same weights, handed to the same kernel through mopo_penalty_from_predictions."""
+    """Through mopo_fakeenv_step on the device's own member outputs, at every shape ((3, 1), D = 4, runs on a
+    two-block head: mopo_bnn_forward_form).  At (3, 1) the same kernel is also reached through
+    mopo_penalty_from_predictions, on the oracle's f32 forward of the same weights in the predict layout."""
     O, A = OA
     c = pk.kernel_case(E, O, A, smv)
-    model = make_model(c['mats'], E, O, A, smv=smv) if O + 1 >= 9 else None
+    model = make_model(c['mats'], E, O, A, smv=smv)
     for B in pk.KERNEL_B:
         for kind in (2, 3):
-            if model is None:
-                pen, em, ev = _c_penalty(c['params'], c['obs'][:B], c['act'][:B], kind)
-            else:
-                pen, em, ev = _c_step(model, c['obs'][:B], c['act'][:B], kind)
-            ref = pk.penalty(kind, em, ev)
-            err = np.abs(pen - ref) / np.where(ref > 0, ref, 1)
-            print('E=%d O=%d smv=%d B=%d kind=%d: max rel err %.3g' % (E, O, smv, B, kind, err.max()))
-            assert (pen >= 0).all() and err.max() <= pk.KERNEL_RTOL
-            if E == 1 and kind == 2:
-                assert not pen.any()
-            if E > 1:   # and not the penalty the field's old reading gave (any non-zero value: max_aleatoric)
-                old = pk.penalty(1, em, ev)
-                assert np.mean(np.abs(pen - old) > 100 * pk.KERNEL_RTOL * old) >= 0.9
+            runs = [_c_step(model, c['obs'][:B], c['act'][:B], kind)]
+            if O + 1 < 9:
+                runs.append(_c_penalty(c['params'], c['obs'][:B], c['act'][:B], kind))
+            for pen, em, ev in runs:
+                ref = pk.penalty(kind, em, ev)
+                err = np.abs(pen - ref) / np.where(ref > 0, ref, 1)
+                print('E=%d O=%d smv=%d B=%d kind=%d: max rel err %.3g' % (E, O, smv, B, kind, err.max()))
+                assert (pen >= 0).all() and err.max() <= pk.KERNEL_RTOL
+                if E == 1 and kind == 2:
+                    assert not pen.any()
+                if E > 1:   # and not the penalty the field's old reading gave (any non-zero value: max_aleatoric)
+                    old = pk.penalty(1, em, ev)
+                    assert np.mean(np.abs(pen - old) > 100 * pk.KERNEL_RTOL * old) >= 0.9
 
 
 # ---- 2. FakeEnv.step against the f64 oracle ----------------------------------------------------------------------
