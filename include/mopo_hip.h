@@ -140,7 +140,22 @@ typedef struct {
   float* d_dev;             /* [B] f32, may be NULL */
   float* d_ens_mean;        /* workspace / output [E, B, D] f32 (required) */
   float* d_ens_var;         /* workspace / output [E, B, D] f32 (required) */
+  /* hard truncation (MOReL's HALT; see "Hard truncation" below); all zero: off, exactly as before the fields existed */
+  int halt;                 /* 0: off (the two fields below are ignored); 1: on */
+  float halt_threshold;     /* a row halts iff !(u <= halt_threshold): u > threshold, or u is NaN */
+  float halt_reward;        /* the penalized reward of a halted row (MOReL's -kappa), e.g. -100 */
 } mopo_fakeenv_args;
+
+/* Hard truncation (no reference counterpart; MOReL's pessimistic MDP on the selected penalty kind u).  The fields
+ * halt / halt_threshold / halt_reward end mopo_fakeenv_args and mopo_rollout_args.  With halt = 1, u is computed
+ * for every row whatever penalty_coeff is, and a row with !(u <= halt_threshold) is halted: its terminal is 1
+ * (d_info_mean's terminal column follows) and its penalized reward is exactly halt_reward (an f32 pool value, or
+ * (double)halt_reward), with no penalty_coeff * u subtracted; the fused loops drop it in the compaction like any
+ * terminal row, and a rollout with halt = 1 and horizon > 1 compacts under MOPO_TERM_NONE too.  Everything else
+ * of a halted row -- next_obs, the unpenalized reward, d_penalty, the member pick and every random draw -- and
+ * every output of a row that is not halted are the bits halt = 0 gives.  Refused (-1, the message names the
+ * field): halt outside {0, 1}; with halt = 1 a halt_reward that is not finite or a NaN halt_threshold.
+ * mopo_rollout_validate ignores the three fields: a segment ends where the data does. */
 
 int mopo_fakeenv_step(mopo_bnn_t h, const mopo_fakeenv_args* a, void* stream);
 
@@ -302,6 +317,13 @@ typedef struct {
   int rollout_random;       /* 1: actions ~ U(-1, 1) instead of the policy's (mopo.py:736-738) */
   const float* d_act_uniform; /* parity mode with rollout_random: [horizon, B, A] injected uniforms, or NULL */
   int actor_dtype;          /* policy forward arithmetic: 0 fp32, 3 bf16x6, 4 f16x3 (mopo_actor_forward_dtype) */
+  /* hard truncation ("Hard truncation" above); all zero: off.  Read by mopo_rollout_run, the staged entry points
+     and mopo_rollout_evaluate; ignored by mopo_rollout_validate */
+  int halt;                 /* 0: off (the two fields below are ignored); 1: on */
+  float halt_threshold;     /* a row halts iff !(u <= halt_threshold) */
+  float halt_reward;        /* the penalized reward of a halted row */
+  int64_t* d_halted;        /* [horizon] rows halted per step, may be NULL (zeros with halt = 0; the run entry
+                               points only) */
 } mopo_rollout_args;
 
 int mopo_rollout_create(mopo_rollout_t* out, mopo_bnn_t bnn, int64_t max_batch, int max_horizon);
@@ -347,7 +369,10 @@ typedef struct {
   uint8_t* d_terminated;    /* [B] 1: the episode ended by the termination rule, 0: it ran T steps */
   double* d_stats;          /* [16]: 0-3 mean / min / max / population std of the returns, 4-7 the same of the
                                lengths, 8 mean penalized return, 9 mean penalty per step (sum of d_pen_sum /
-                               sum of d_length), 10 terminated fraction, 11 B, 12-15 zero */
+                               sum of d_length), 10 terminated fraction, 11 B, 12 halted fraction (zero with
+                               halt = 0), 13-15 zero */
+  uint8_t* d_halted;        /* [B] 1: the episode ended by HALT (mopo_rollout_args.halt); d_terminated stays "ended
+                               by the termination rule", and a step on which both fire sets both */
 } mopo_eval_args;
 
 /* `a` as for mopo_rollout_run, its parity-mode streams indexed [step][B] by the current compacted row,
@@ -403,6 +428,17 @@ typedef struct {
  * bit-reproducible. */
 int mopo_rollout_validate(mopo_rollout_t h, const mopo_rollout_args* a, const mopo_pool_desc* pool,
                           const mopo_val_args* v, void* stream);
+
+/* ---- the penalty over a dataset ----------------------------------------------------------------
+ * d_u[j] = u(observations[j], actions[j]) of penalty kind `kind` (MOPO_PENALTY_*) for pool rows j < n_rows <=
+ * pool->max_size: the distribution a halt_threshold is calibrated on.  Chunks of the handle's max_batch on one
+ * stream, no host synchronisation; per chunk a gather of the ensemble's scaled input rows straight from the pool's
+ * f32 fields, one ensemble forward and the kind's reduction.  Nothing is drawn or sampled, no policy runs and the
+ * pool is only read; u has the bits mopo_rollout_run's first step computes from the same rows.  Refused: a kind
+ * outside the enum, n_rows < 0 or > max_size, NULL pool fields or d_u.  n_rows = 0 returns 0.  No reference
+ * counterpart. */
+int mopo_rollout_penalty_profile(mopo_rollout_t h, const mopo_pool_desc* pool, int64_t n_rows, int kind,
+                                 float* d_u /* [n_rows] */, void* stream);
 
 /* ---- SAC update (MOPO._do_training + _update_target) ------------------------------------
  * h_params: initial flat parameters (mopo_sac_param_count floats, layout above); target = copy

@@ -15,8 +15,9 @@ or ``$D4RL_DATASET_DIR/<task>.npz`` named after the config's ``pool_load_path`` 
 (the forward arithmetic; default f16x3, held to the fp32 parity tolerances) and ``--model-eval-episodes`` /
 ``--model-eval-length`` (episodes of the policy inside the learned model after every epoch; off by default),
 ``--model-val-segments`` / ``--model-val-horizon`` (open-loop validation of the trained model on the dataset's
-own trajectories; off by default) and ``--penalty-kind`` (the reward penalty, mopo_amd.fake_env.PENALTY_KINDS;
-default: the config's choice).
+own trajectories; off by default), ``--penalty-kind`` (the reward penalty, mopo_amd.fake_env.PENALTY_KINDS;
+default: the config's choice) and ``--halt-threshold`` or ``--halt-quantile`` with ``--halt-reward`` (hard
+truncation of the model rollouts where the penalty exceeds the threshold; off by default).
 ``--config`` is any
 importable module holding a ``params`` dict (examples/development/__init__.py:19-22), or one of the
 restated D4RL config names when the reference's ``examples`` package is not installed.
@@ -51,6 +52,8 @@ def get_parser():
     p.add_argument('--model-val-segments', type=int, default=None)
     p.add_argument('--model-val-horizon', type=int, default=None)
     p.add_argument('--penalty-kind', default=None, choices=PENALTY_KINDS)
+    for f in ('--halt-threshold', '--halt-quantile', '--halt-reward'):
+        p.add_argument(f, type=float, default=None)
     for f in ('--cpus', '--gpus', '--trial-cpus', '--trial-extra-cpus', '--max-failures'):
         p.add_argument(f, type=int, default=None)
     for f in ('--trial-gpus', '--trial-extra-gpus'):
@@ -80,11 +83,12 @@ def variant_spec(args):
     params = get_params(args.config)
     kw = params['kwargs']
     for k in ('ensemble_dtype', 'actor_dtype', 'model_eval_episodes', 'model_eval_length', 'model_val_segments',
-              'model_val_horizon', 'penalty_kind'):
+              'model_val_horizon', 'penalty_kind', 'halt_threshold', 'halt_quantile', 'halt_reward'):
         if getattr(args, k) is not None:
             kw[k] = getattr(args, k)
-    from .config import resolve_penalty_kind
+    from .config import check_halt_kwargs, resolve_penalty_kind
     resolve_penalty_kind(kw)
+    check_halt_kwargs(kw)
     kw.setdefault('ensemble_dtype', default_ensemble_dtype(kw.get('hidden_dim', 200)))
     seeds = [args.seed + i for i in range(max(args.num_samples, 1))]
     return {'algorithm_params': params, 'run_params': {'seeds': seeds, 'checkpoint_frequency': args.checkpoint_frequency},
@@ -116,7 +120,7 @@ def main(argv=None):
         if args.epochs is not None:
             rargv += ['--epochs', str(args.epochs)]
         for k in ('ensemble_dtype', 'actor_dtype', 'model_eval_episodes', 'model_eval_length', 'model_val_segments',
-              'model_val_horizon', 'penalty_kind'):
+              'model_val_horizon', 'penalty_kind', 'halt_threshold', 'halt_quantile', 'halt_reward'):
             if getattr(args, k) is not None:
                 rargv += ['--' + k.replace('_', '-'), str(getattr(args, k))]
         run.main(rargv)

@@ -21,7 +21,9 @@ class FakeEnvArgs(C.Structure):
                 ('d_next_obs', c_void_p), ('d_rewards', c_void_p), ('d_terminals', c_void_p),
                 ('d_penalty', c_void_p), ('d_unpenalized', c_void_p), ('d_info_mean', c_void_p),
                 ('d_info_std', c_void_p), ('d_log_prob', c_void_p), ('d_dev', c_void_p),
-                ('d_ens_mean', c_void_p), ('d_ens_var', c_void_p)]
+                ('d_ens_mean', c_void_p), ('d_ens_var', c_void_p),
+                # hard truncation (include/mopo_hip.h "Hard truncation"); left out they are 0: off
+                ('halt', c_int), ('halt_threshold', c_float), ('halt_reward', c_float)]
 
 
 class PoolDesc(C.Structure):
@@ -36,12 +38,15 @@ class RolloutArgs(C.Structure):
                 ('term_kind', c_int), ('seed', c_u64), ('epoch', c_u32), ('uid_offset', c_i64),
                 ('d_eps_act', c_void_p), ('d_eps_obs', c_void_p), ('d_model_inds', c_void_p),
                 ('d_steps', c_void_p), ('penalty_learned_var', c_int), ('deterministic', c_int),
-                ('rollout_random', c_int), ('d_act_uniform', c_void_p), ('actor_dtype', c_int)]
+                ('rollout_random', c_int), ('d_act_uniform', c_void_p), ('actor_dtype', c_int),
+                # hard truncation; left out they are 0 / NULL: off
+                ('halt', c_int), ('halt_threshold', c_float), ('halt_reward', c_float), ('d_halted', c_void_p)]
 
 
 class EvalArgs(C.Structure):
     _fields_ = [('policy_deterministic', c_int), ('d_return', c_void_p), ('d_pen_return', c_void_p),
-                ('d_pen_sum', c_void_p), ('d_length', c_void_p), ('d_terminated', c_void_p), ('d_stats', c_void_p)]
+                ('d_pen_sum', c_void_p), ('d_length', c_void_p), ('d_terminated', c_void_p), ('d_stats', c_void_p),
+                ('d_halted', c_void_p)]
 
 
 class ValArgs(C.Structure):
@@ -105,6 +110,7 @@ SIGNATURES = {
     'mopo_rollout_evaluate': (c_int, [c_void_p, C.POINTER(RolloutArgs), C.POINTER(EvalArgs), c_void_p]),
     'mopo_rollout_validate': (c_int, [c_void_p, C.POINTER(RolloutArgs), C.POINTER(PoolDesc), C.POINTER(ValArgs),
                                       c_void_p]),
+    'mopo_rollout_penalty_profile': (c_int, [c_void_p, C.POINTER(PoolDesc), c_i64, c_int, c_void_p, c_void_p]),
     'mopo_rollout_profile': (c_int, [c_void_p, c_int]),
     'mopo_rollout_profile_read': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     'mopo_sac_create': (c_int, [C.POINTER(c_void_p), c_int, c_int, c_int, c_int, c_int, c_void_p, c_float,

@@ -98,6 +98,26 @@ def resolve_penalty_kind(kwargs):
     return kwargs
 
 
+def check_halt_kwargs(kwargs):
+    """The hard-truncation kwargs of a config (or ``--halt-threshold`` / ``--halt-quantile`` / ``--halt-reward``):
+    at most one of ``halt_threshold`` and ``halt_quantile`` (0 < q <= 1), and with either a finite
+    ``halt_reward``; none of them: no halting.  Raises ``ValueError``; returns ``kwargs``."""
+    import math
+    thr, q, rew = (kwargs.get(k) for k in ('halt_threshold', 'halt_quantile', 'halt_reward'))
+    if thr is not None and q is not None:
+        raise ValueError('halt_threshold and halt_quantile are two ways to set one threshold: give one')
+    if q is not None and not 0.0 < float(q) <= 1.0:
+        raise ValueError('halt_quantile must satisfy 0 < q <= 1 (got %r)' % (q,))
+    if thr is not None and math.isnan(float(thr)):
+        raise ValueError('halt_threshold must not be NaN')
+    if thr is not None or q is not None:
+        if rew is None:
+            raise ValueError('halt_threshold / halt_quantile need a halt_reward (the reward of a halted row, e.g. -100)')
+        if not math.isfinite(float(rew)):
+            raise ValueError('halt_reward must be finite (got %r)' % (rew,))
+    return kwargs
+
+
 def load_module_params(name, params_name='params'):
     """examples/development/__init__.py:19-22: ``importlib.import_module(name).params``; None when
     the module itself does not exist (an import error raised INSIDE an existing module propagates)."""
@@ -127,6 +147,7 @@ def get_params(name):
             raise KeyError('config %r: params has no %r' % (name, k))
     p = deep_update(DEFAULTS, params, ADDITIONAL)
     resolve_penalty_kind(p['kwargs'])   # a config's own 'penalty_kind' kwarg
+    check_halt_kwargs(p['kwargs'])
     # softlearning/algorithms/utils.py:43-48: model_name = exp_name with '-' + '_smv' + '_1_0' (always set)
     p['kwargs']['model_name'] = (p['exp_name'].replace('_', '-') +
                                  ('_smv' if p['kwargs'].get('separate_mean_var') else '') + '_1_0')

@@ -80,10 +80,10 @@ __global__ __launch_bounds__(256) void fakeenv_post_kernel(const mopo_fakeenv_ar
     }
   }
   // termination on the f64 next_obs (fake_env.py:90-91)
-  const bool term = term_fn_at(a.term_kind, [&](int d) { return sample_at(d + 1); }, O);
-  // penalty (fake_env.py:97-115)
+  const bool rule = term_fn_at(a.term_kind, [&](int d) { return sample_at(d + 1); }, O);
+  // penalty (fake_env.py:97-115); a halt reads it whatever the coefficient
   float pen = 0.f;
-  if (a.penalty_coeff != 0.f) {
+  if (a.penalty_coeff != 0.f || a.halt == 1) {
     if (pen_ready) {
       pen = pen_ready[b];
     } else if (a.penalty_learned_var) {
@@ -109,11 +109,15 @@ __global__ __launch_bounds__(256) void fakeenv_post_kernel(const mopo_fakeenv_ar
     }
   }
   const double rew = sample_at(0);
-  const double pen_rew = a.penalty_coeff != 0.f ? rew - (double)a.penalty_coeff * (double)pen : rew;
+  // hard truncation (mopo_hip.h "Hard truncation"; the fused loops: rollout_post.h post_conclude)
+  const bool halted = a.halt == 1 && !(pen <= a.halt_threshold);
+  const bool term = rule || halted;
+  const double pen_rew = halted ? (double)a.halt_reward
+                                : (a.penalty_coeff != 0.f ? rew - (double)a.penalty_coeff * (double)pen : rew);
   for (int d = 0; d < O; ++d) a.d_next_obs[b * O + d] = sample_at(d + 1);
   a.d_rewards[b] = pen_rew;
   a.d_terminals[b] = term ? 1 : 0;
-  if (a.d_penalty) a.d_penalty[b] = pen;
+  if (a.d_penalty) a.d_penalty[b] = a.penalty_coeff != 0.f ? pen : 0.f;   // as with halt = 0
   if (a.d_unpenalized) a.d_unpenalized[b] = rew;
   if (a.d_info_mean) {  // fake_env.py:94-95
     float* im = a.d_info_mean + b * (D + 1);
@@ -140,6 +144,7 @@ extern "C" int mopo_fakeenv_step(mopo_bnn_t hh, const mopo_fakeenv_args* a, void
                "be >= 2)");
   MOPO_REQUIRE(a->penalty_learned_var >= 0 && a->penalty_learned_var < MOPO_PENALTY_KINDS,
                std::string("mopo_fakeenv_step") + kPenaltyKindMsg);
+  if (check_halt(a->halt, a->halt_threshold, a->halt_reward, "mopo_fakeenv_step")) return -1;
   if (a->B == 0) return 0;  // empty batch: nothing to read or write (empty buffers may be NULL)
   MOPO_REQUIRE(a->d_ens_mean && a->d_ens_var, "mopo_fakeenv_step: ensemble workspaces required");
   MOPO_REQUIRE(a->deterministic || (a->d_noise_sel && a->d_model_inds),
@@ -156,7 +161,7 @@ extern "C" int mopo_fakeenv_step(mopo_bnn_t hh, const mopo_fakeenv_args* a, void
   f.var = a->d_ens_var;
   if (launch_bnn_fwd(h, FWD_PREDICT, f, s)) return -1;
   const float* pen_ready = nullptr;
-  if (a->penalty_learned_var >= MOPO_PENALTY_MAX_PAIRWISE && a->penalty_coeff != 0.f) {
+  if (a->penalty_learned_var >= MOPO_PENALTY_MAX_PAIRWISE && (a->penalty_coeff != 0.f || a->halt == 1)) {
     // the predict layout [E][B][D], variances; into the handle's [B] scratch (earlier steps of this handle
     // ran on this stream: one handle = one stream at a time)
     if (h->pen_rows < a->B) {

@@ -14,6 +14,15 @@ namespace mopo {
 const char* const kPenaltyKindMsg =
     ": unknown penalty kind (0 mean_distance, 1 max_aleatoric, 2 max_pairwise, 3 ensemble_std)";
 
+int check_halt(int halt, float halt_threshold, float halt_reward, const char* who) {
+  const std::string w(who);
+  MOPO_REQUIRE(halt == 0 || halt == 1, w + ": halt must be 0 (off) or 1 (on)");
+  if (!halt) return 0;
+  MOPO_REQUIRE(std::isfinite(halt_reward), w + ": halt_reward must be finite when halt = 1");
+  MOPO_REQUIRE(!std::isnan(halt_threshold), w + ": halt_threshold must not be NaN when halt = 1");
+  return 0;
+}
+
 // PEN_RPB rows per block, one 32-lane group per row and one lane per output dim d < D = O + 1, as
 // rollout_post_kernel lays rows out: every load of a member's D values is contiguous across the row's lanes.
 // Each lane keeps running scalars only (no per-thread arrays indexed by the runtime E or D: they would live

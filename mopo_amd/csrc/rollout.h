@@ -43,7 +43,7 @@ struct Rollout {
   // episodes, the zero policy noise [Bmax][A] of the deterministic policy, the statistics
   void* eval_mem = nullptr;
   double* ev_ret; double* ev_pen_ret; double* ev_pen_sum;
-  int32_t* ev_len; uint8_t* ev_term; float* ev_eps0; double* ev_stats;
+  int32_t* ev_len; uint8_t* ev_term; float* ev_eps0; double* ev_stats; uint8_t* ev_halt;
   // open-loop validation (rollout_val.hip), allocated on first use: the segments' start rows [Bmax] (as
   // drawn, and clamped into the pool for the start gather), and the [K][B] tables / statistics a caller
   // left NULL (val_tab, grown to the largest K * B asked for)
@@ -87,6 +87,11 @@ struct PostArgs {
   int E;
   int64_t all_stride;
   int pen_dist, det;
+  // hard truncation (mopo_hip.h "Hard truncation"): halt 1 -> a row with !(penalty <= halt_threshold) is terminal
+  // with the reward halt_reward; halted_cnt: this step's count of such rows (one atomic per block), or NULL
+  int halt;
+  float halt_threshold, halt_reward;
+  unsigned long long* halted_cnt;
 };
 
 // FakeEnv's modes for one call: deterministic steps, the mean-distance penalty (computed by the post kernel),
@@ -100,8 +105,8 @@ struct StepModes {
 // The checks every entry point `who` makes on its arguments: B, term_kind, the penalty kind, the elites (an
 // entry point that runs no policy needs none for deterministic steps) and, with a policy, actor_dtype.
 int rollout_check_args(const Rollout* h, const mopo_rollout_args* a, const char* who, bool policy);
-// The modes of `a` (always_pen: the penalty is computed whatever the coefficient); allocates mean_all /
-// std_all on first use.
+// The modes of `a` (always_pen: the penalty is computed whatever the coefficient, as it is with a->halt = 1);
+// allocates mean_all / std_all on first use.
 int rollout_modes(Rollout* h, const mopo_rollout_args* a, bool always_pen, StepModes* m);
 // The start states (rollout_start_kernel): a's B rows gathered from env_obs rows idx (NULL: drawn over
 // [0, env_size)) into obs[0], their ids into uid[0], the live counts of the nsplit parts of bpart rows.

@@ -7,6 +7,8 @@
 //                     max-over-members aleatoric norm (fake_env.py:66-81, 110) -> no [E,B,D] in HBM
 //   rollout_post      sample, reward penalty, termination, next_obs/rew/term half of the pool row
 //                     (fake_env.py:72, 90-115; mopo.py:750-751)
+//                     and, with mopo_rollout_args.halt, hard truncation: a row whose penalty exceeds the
+//                     threshold is terminal at halt_reward (rollout_post.h post_conclude)
 //   rollout_compact   order-preserving non-terminal compaction  obs = next_obs[~term] (mopo.py:753-758)
 //   step_advance      steps_added / pool pointer & size (mopo.py:748; flexible_replay_pool.py:45-48)
 #include "mlp_tile.h"
@@ -126,17 +128,18 @@ __global__ __launch_bounds__(256) void rollout_post_kernel(const PostArgs a) {
     a.pool.d_next_obs[pos * O + sub - 1] = (float)s;
   }
   if (sub == 0) {
-    bool keep = false;
+    int keep = 0;
     if (live) {
       const PostVerdict v = post_verdict(a, row, srow[rl], s, pen_d);
       a.pool.d_rew[pos] = (float)v.pr;
       a.pool.d_term[pos] = v.term ? 1 : 0;
-      keep = !v.term;
-      if (a.keep) a.keep[row] = keep ? 1 : 0;
+      keep = post_kept_word(v);
+      if (a.keep) a.keep[row] = keep & 1;
     }
-    kept[rl] = keep ? 1 : 0;
+    kept[rl] = keep;
   }
-  if (a.blockcnt) post_count_kept<POST_RPB>(kept, a.blockcnt, (int64_t)blockIdx.x * POST_RPB);
+  if (a.blockcnt || a.halted_cnt)
+    post_count_kept<POST_RPB>(kept, a.blockcnt, a.halted_cnt, (int64_t)blockIdx.x * POST_RPB);
 }
 
 // The same post-processing for the common case (sampled steps, max-aleatoric penalty: neither pen_dist
@@ -173,21 +176,18 @@ __global__ __launch_bounds__(1024) void rollout_post_flat_kernel(const PostArgs 
   }
   if (tid < POSTF_ROWS) {
     const int64_t rr = r0 + tid;
-    bool keep = false;
+    int keep = 0;
     if (rr < count) {
-      const bool term = term_fn(a.term_kind, &srow[tid][1], O);        // fake_env.py:91
-      const double s0 = srow[tid][0];
-      const float pen = __uint_as_float(a.pen[rr]);
-      const double pr = a.coeff != 0.f ? s0 - (double)a.coeff * (double)pen : s0;   // fake_env.py:115
+      const PostVerdict v = post_verdict(a, rr, srow[tid], srow[tid][0], 0.f);   // fake_env.py:91, 115
       const int64_t pos = spos[tid];
-      a.pool.d_rew[pos] = (float)pr;
-      a.pool.d_term[pos] = term ? 1 : 0;
-      keep = !term;
-      if (a.keep) a.keep[rr] = keep ? 1 : 0;
+      a.pool.d_rew[pos] = (float)v.pr;
+      a.pool.d_term[pos] = v.term ? 1 : 0;
+      keep = post_kept_word(v);
+      if (a.keep) a.keep[rr] = keep & 1;
     }
-    kept[tid] = keep ? 1 : 0;
+    kept[tid] = keep;
   }
-  if (a.blockcnt) post_count_kept<POSTF_ROWS>(kept, a.blockcnt, r0);
+  if (a.blockcnt || a.halted_cnt) post_count_kept<POSTF_ROWS>(kept, a.blockcnt, a.halted_cnt, r0);
 }
 
 __global__ __launch_bounds__(PB) void rollout_compact_kernel(int O, const int* blockcnt, const uint8_t* keepf,
@@ -283,7 +283,7 @@ int rollout_check_args(const Rollout* h, const mopo_rollout_args* a, const char*
 }
 
 int rollout_modes(Rollout* h, const mopo_rollout_args* a, bool always_pen, StepModes* m) {
-  const bool pen = always_pen || a->penalty_coeff != 0.f;
+  const bool pen = always_pen || a->penalty_coeff != 0.f || a->halt == 1;   // a halt reads u at every row
   m->det = a->deterministic != 0;
   m->pen_dist = a->penalty_learned_var == 0 && pen;
   // kinds >= 2 (penalty.hip): every member's mean and std, reduced by one kernel behind the ensemble
@@ -361,6 +361,8 @@ PostArgs rollout_post_args(const Rollout* h, const mopo_rollout_args* a, const S
   pa.stage_base = -1;
   pa.mean_all = m.need_all ? h->mean_all + off * D : nullptr; pa.E = h->bnn->E; pa.all_stride = h->Bmax;
   pa.pen_dist = m.pen_dist; pa.det = m.det;
+  pa.halt = a->halt == 1; pa.halt_threshold = a->halt_threshold; pa.halt_reward = a->halt_reward;
+  pa.halted_cnt = pa.halt && a->d_halted ? reinterpret_cast<unsigned long long*>(a->d_halted) + i : nullptr;
   return pa;
 }
 
@@ -404,7 +406,8 @@ int rollout_none_alive(Rollout* h, hipStream_t s, bool* none) {
 static int run_impl(Rollout* h, const mopo_rollout_args* a, const mopo_pool_desc* p, bool staged, int i0, int i1,
                     hipStream_t s) {
   MOPO_REQUIRE(a && p, "rollout: NULL argument");
-  if (rollout_check_args(h, a, "rollout", true)) return -1;
+  if (rollout_check_args(h, a, "rollout", true) || check_halt(a->halt, a->halt_threshold, a->halt_reward, "rollout"))
+    return -1;
   MOPO_REQUIRE(a->horizon >= 0 && a->horizon <= h->Hmax, "rollout: horizon exceeds max_horizon");
   MOPO_REQUIRE(a->d_env_obs && a->env_size > 0, "rollout: empty env pool");
   MOPO_REQUIRE(a->d_pi_params, "rollout: NULL policy params");
@@ -423,7 +426,8 @@ static int run_impl(Rollout* h, const mopo_rollout_args* a, const mopo_pool_desc
   const bool post_flat = pf ? std::atoi(pf) != 0 : true;
   // live rows are compacted between steps (mopo.py:758); a one-step rollout never needs it: its
   // rows, terminal or not, all enter the pool (mopo.py:750-751) and no next step reads them
-  const bool compact = a->term_kind != MOPO_TERM_HALFCHEETAH && a->horizon > 1;
+  // (a halt ends rows under every termination rule, the never-done ones included)
+  const bool compact = (a->term_kind != MOPO_TERM_HALFCHEETAH || a->halt == 1) && a->horizon > 1;
   // no compaction, pool layout: positions advance by B per step and one launch advances the pool
   const bool batched_advance = !compact && !staged;
   // Split rollout (pool or staged layout): with no compaction the rows never interact, so two halves run their own
@@ -439,6 +443,7 @@ static int run_impl(Rollout* h, const mopo_rollout_args* a, const mopo_pool_desc
     h->oc = 0;
     h->uc = 0;
     KTimer t(h, KC_START, s);
+    if (a->d_halted) MOPO_HIP(hipMemsetAsync(a->d_halted, 0, (size_t)a->horizon * sizeof(int64_t), s));
     if (rollout_start(h, a, a->d_env_obs, a->env_size, a->d_start_idx, nsplit, bpart, s)) return -1;
   }
   if (i0 == 0) {

@@ -22,14 +22,15 @@ struct EvalPostArgs {
   double* pen_ret;          // [B] += the penalized reward (fake_env.py:115)
   double* pen_sum;          // [B] += the penalty
   int32_t* len;             // [B] += 1
-  uint8_t* terminated;      // [B] = 1 on termination
+  uint8_t* terminated;      // [B] = 1 on termination by the rule
+  uint8_t* halted;          // [B] = 1 on a halt
 };
 
 __global__ void rollout_eval_init_kernel(int64_t B, double* ret, double* pen_ret, double* pen_sum, int32_t* len,
-                                         uint8_t* terminated) {
+                                         uint8_t* terminated, uint8_t* halted) {
   const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (i >= B) return;
-  ret[i] = 0.0; pen_ret[i] = 0.0; pen_sum[i] = 0.0; len[i] = 0; terminated[i] = 0;
+  ret[i] = 0.0; pen_ret[i] = 0.0; pen_sum[i] = 0.0; len[i] = 0; terminated[i] = 0; halted[i] = 0;
 }
 
 // One FakeEnv step (rollout_post.h) for POST_RPB rows per block, a 32-lane group per row.  Its own part: a live
@@ -49,7 +50,7 @@ __global__ __launch_bounds__(256) void rollout_eval_post_kernel(const EvalPostAr
   __syncthreads();
   if (on && sub >= 1) a.obs_next[row * O + sub - 1] = s;           // next_obs = samples[:, 1:] (:90)
   if (sub == 0) {
-    bool keep = false;
+    int keep = 0;
     if (live) {
       const PostVerdict v = post_verdict(a, row, srow[rl], s, pen_d);
       const int64_t ep = a.uid[row] - ea.uid_offset;               // in [0, B): the start kernel's ids
@@ -57,13 +58,14 @@ __global__ __launch_bounds__(256) void rollout_eval_post_kernel(const EvalPostAr
       ea.pen_ret[ep] += v.pr;
       ea.pen_sum[ep] += (double)v.pen;
       ea.len[ep] += 1;
-      if (v.term) ea.terminated[ep] = 1;
-      keep = !v.term;
-      if (a.keep) a.keep[row] = keep ? 1 : 0;
+      if (v.rule) ea.terminated[ep] = 1;
+      if (v.halted) ea.halted[ep] = 1;
+      keep = post_kept_word(v);
+      if (a.keep) a.keep[row] = keep & 1;
     }
-    kept[rl] = keep ? 1 : 0;
+    kept[rl] = keep;
   }
-  if (a.blockcnt) post_count_kept<POST_RPB>(kept, a.blockcnt, (int64_t)blockIdx.x * POST_RPB);
+  if (a.blockcnt) post_count_kept<POST_RPB>(kept, a.blockcnt, nullptr, (int64_t)blockIdx.x * POST_RPB);
 }
 
 __global__ void rollout_eval_advance_kernel(int* cnt, int64_t* steps, int i) {
@@ -80,11 +82,11 @@ __global__ void rollout_eval_steps_kernel(const int* cnt, int64_t* steps, int T)
 // t + 256, ... in that order, then a fixed binary tree over the 256 partials -- the same bits every run.
 // The standard deviations take a second pass around the mean (np.std: population).
 constexpr int ST = 256;
-enum { SQ_RET = 0, SQ_LEN, SQ_PRET, SQ_PEN, SQ_TERM, SQ_RMIN, SQ_LMIN, SQ_RMAX, SQ_LMAX, SQ_N };
+enum { SQ_RET = 0, SQ_LEN, SQ_PRET, SQ_PEN, SQ_TERM, SQ_HALT, SQ_RMIN, SQ_LMIN, SQ_RMAX, SQ_LMAX, SQ_N };
 __global__ __launch_bounds__(ST) void rollout_eval_stats_kernel(const double* ret, const double* pen_ret,
                                                                 const double* pen_sum, const int32_t* len,
-                                                                const uint8_t* terminated, int64_t B,
-                                                                double* stats) {
+                                                                const uint8_t* terminated, const uint8_t* halted,
+                                                                int64_t B, double* stats) {
   __shared__ double red[SQ_N][ST];
   const int tid = threadIdx.x;
   auto tree = [&](int nq) {   // quantities [0, SQ_RMIN) sum, [SQ_RMIN, SQ_RMAX) min, the rest max
@@ -103,7 +105,7 @@ __global__ __launch_bounds__(ST) void rollout_eval_stats_kernel(const double* re
   for (int64_t i = tid; i < B; i += ST) {
     const double r = ret[i], l = (double)len[i];
     v[SQ_RET] += r; v[SQ_LEN] += l; v[SQ_PRET] += pen_ret[i]; v[SQ_PEN] += pen_sum[i];
-    v[SQ_TERM] += (double)terminated[i];
+    v[SQ_TERM] += (double)terminated[i]; v[SQ_HALT] += (double)halted[i];
     v[SQ_RMIN] = fmin(v[SQ_RMIN], r); v[SQ_LMIN] = fmin(v[SQ_LMIN], l);
     v[SQ_RMAX] = fmax(v[SQ_RMAX], r); v[SQ_LMAX] = fmax(v[SQ_LMAX], l);
   }
@@ -118,7 +120,8 @@ __global__ __launch_bounds__(ST) void rollout_eval_stats_kernel(const double* re
     stats[9] = red[SQ_PEN][0] / lsum;
     stats[10] = red[SQ_TERM][0] / n;
     stats[11] = n;
-    stats[12] = stats[13] = stats[14] = stats[15] = 0.0;
+    stats[12] = red[SQ_HALT][0] / n;
+    stats[13] = stats[14] = stats[15] = 0.0;
   }
   __syncthreads();   // red is read above by every thread before the second pass overwrites it
   double dr = 0.0, dl = 0.0;
@@ -142,7 +145,9 @@ extern "C" int mopo_rollout_evaluate(mopo_rollout_t hh, const mopo_rollout_args*
                                      void* stream) {
   Rollout* h = reinterpret_cast<Rollout*>(hh);
   MOPO_REQUIRE(h && a && e, "mopo_rollout_evaluate: NULL argument");
-  if (rollout_check_args(h, a, "mopo_rollout_evaluate", true)) return -1;
+  if (rollout_check_args(h, a, "mopo_rollout_evaluate", true) ||
+      check_halt(a->halt, a->halt_threshold, a->halt_reward, "mopo_rollout_evaluate"))
+    return -1;
   MOPO_REQUIRE(a->horizon >= 1 && a->horizon <= 4095,
                "mopo_rollout_evaluate: the episode length T must be in [1, 4095] (the Philox step key is "
                "epoch * 4096 + 1 + step)");
@@ -157,23 +162,24 @@ extern "C" int mopo_rollout_evaluate(mopo_rollout_t hh, const mopo_rollout_args*
   Bnn* bnn = h->bnn;
   const int A = bnn->A, T = a->horizon;
   const int64_t B = a->B;
-  const bool compact = a->term_kind != MOPO_TERM_HALFCHEETAH;
+  const bool compact = a->term_kind != MOPO_TERM_HALFCHEETAH || a->halt == 1;   // a halt ends episodes anywhere
 
   if (!h->eval_mem) {
     const size_t n = (size_t)h->Bmax;
-    size_t sz[] = {n * 8, n * 8, n * 8, n * 4, n, n * A * 4, 16 * 8};
-    size_t off[7];
-    MOPO_HIP(hipMalloc(&h->eval_mem, carve(sz, 7, off)));
+    size_t sz[] = {n * 8, n * 8, n * 8, n * 4, n, n * A * 4, 16 * 8, n};
+    size_t off[8];
+    MOPO_HIP(hipMalloc(&h->eval_mem, carve(sz, 8, off)));
     char* m = (char*)h->eval_mem;
     h->ev_ret = (double*)(m + off[0]); h->ev_pen_ret = (double*)(m + off[1]); h->ev_pen_sum = (double*)(m + off[2]);
     h->ev_len = (int32_t*)(m + off[3]); h->ev_term = (uint8_t*)(m + off[4]); h->ev_eps0 = (float*)(m + off[5]);
-    h->ev_stats = (double*)(m + off[6]);
+    h->ev_stats = (double*)(m + off[6]); h->ev_halt = (uint8_t*)(m + off[7]);
   }
   double* ret = e->d_return ? e->d_return : h->ev_ret;
   double* pen_ret = e->d_pen_return ? e->d_pen_return : h->ev_pen_ret;
   double* pen_sum = e->d_pen_sum ? e->d_pen_sum : h->ev_pen_sum;
   int32_t* len = e->d_length ? e->d_length : h->ev_len;
   uint8_t* terminated = e->d_terminated ? e->d_terminated : h->ev_term;
+  uint8_t* halted = e->d_halted ? e->d_halted : h->ev_halt;
   double* stats = e->d_stats ? e->d_stats : h->ev_stats;
 
   StepModes m;
@@ -181,7 +187,7 @@ extern "C" int mopo_rollout_evaluate(mopo_rollout_t hh, const mopo_rollout_args*
 
   h->next_step = 0;   // a staged step range must not continue across an evaluation
   hipLaunchKernelGGL(rollout_eval_init_kernel, dim3(ceil_div((int)B, 256)), dim3(256), 0, s, B, ret, pen_ret,
-                     pen_sum, len, terminated);
+                     pen_sum, len, terminated, halted);
   MOPO_HIP(hipGetLastError());
   if (a->d_steps) MOPO_HIP(hipMemsetAsync(a->d_steps, 0, (size_t)T * sizeof(int64_t), s));
   // the deterministic policy: pi = mu + std * 0 through the sampled path, actor_finish untouched
@@ -206,6 +212,7 @@ extern "C" int mopo_rollout_evaluate(mopo_rollout_t hh, const mopo_rollout_args*
     ea.p = rollout_post_args(h, a, m, i, oc, uc, 0, h->cnt, compact);
     ea.uid_offset = a->uid_offset;
     ea.ret = ret; ea.pen_ret = pen_ret; ea.pen_sum = pen_sum; ea.len = len; ea.terminated = terminated;
+    ea.halted = halted; ea.p.halted_cnt = nullptr;   // per episode here, not per step
     if (compact && rollout_zero_chunks(h, B, s)) return -1;
     hipLaunchKernelGGL(rollout_eval_post_kernel, dim3(ceil_div((int)B, POST_RPB)), dim3(256), 0, s, ea);
     MOPO_HIP(hipGetLastError());
@@ -226,8 +233,8 @@ extern "C" int mopo_rollout_evaluate(mopo_rollout_t hh, const mopo_rollout_args*
   }
   if (!compact && a->d_steps)   // the live count never changed
     hipLaunchKernelGGL(rollout_eval_steps_kernel, dim3(1), dim3(256), 0, s, h->cnt, a->d_steps, T);
-  hipLaunchKernelGGL(rollout_eval_stats_kernel, dim3(1), dim3(ST), 0, s, ret, pen_ret, pen_sum, len, terminated, B,
-                     stats);
+  hipLaunchKernelGGL(rollout_eval_stats_kernel, dim3(1), dim3(ST), 0, s, ret, pen_ret, pen_sum, len, terminated, halted,
+                     B, stats);
   MOPO_HIP(hipGetLastError());
   return 0;
 }

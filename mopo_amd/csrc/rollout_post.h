@@ -4,6 +4,7 @@
 // slice), the row's verdict (termination, penalty, penalized reward) and the kept-rows count of a block.  Each
 // kernel keeps its own epilogue: pool half-rows, episode accumulators, error tables.
 #pragma once
+#include "penalty.h"
 #include "rollout.h"
 
 namespace mopo {
@@ -45,20 +46,8 @@ __device__ __forceinline__ double post_group_step(const PostArgs& a, int64_t row
     const float m = a.mean_all[((int64_t)e * a.all_stride + row) * D + sub];
     return sub >= 1 ? (float)((double)m + ob) : m;
   };
-  pen_d = 0.f;
-  if (a.pen_dist) {  // max_e || mean_e - mean_e' mean_e' || over the obs dims (fake_env.py:98-108)
-    float sum = 0.f;
-    if (on && sub >= 1)
-      for (int e = 0; e < a.E; ++e) sum += member_mean(e);
-    const float avg = sum / (float)a.E;                           // np.mean(axis=0), f32
-    for (int e = 0; e < a.E; ++e) {
-      const float dd = on && sub >= 1 ? member_mean(e) - avg : 0.f;
-      float q = dd * dd;
-#pragma unroll
-      for (int o = 16; o >= 1; o >>= 1) q += __shfl_xor(q, o);       // the row's 32-lane group
-      pen_d = fmaxf(pen_d, sqrtf(q));
-    }
-  }
+  // max_e || mean_e - mean_e' mean_e' || over the obs dims (fake_env.py:98-108; penalty.h)
+  pen_d = a.pen_dist ? mean_distance_penalty(member_mean, a.E, on && sub >= 1) : 0.f;
   if (on && a.det) {  // samples = mean over ALL members of the means (fake_env.py:69-70, 84-86)
     float acc = 0.f;
     for (int e = 0; e < a.E; ++e) acc += member_mean(e);
@@ -75,29 +64,44 @@ __device__ __forceinline__ double post_group_step(const PostArgs& a, int64_t row
 
 // What lane 0 of a live row concludes from the row's LDS slice (after the barrier) and its own s = samples[:, 0]
 struct PostVerdict {
-  bool term;    // fake_env.py:91
+  bool term;    // fake_env.py:91, or halted
+  bool rule;    // fake_env.py:91 alone: the termination rule's verdict
+  bool halted;  // hard truncation: !(pen <= halt_threshold)
   float pen;    // the penalty of the selected kind
-  double pr;    // rewards = samples[:, :1] - coeff * penalty (fake_env.py:115)
+  double pr;    // rewards = samples[:, :1] - coeff * penalty (fake_env.py:115); a halted row's: halt_reward
 };
-__device__ __forceinline__ PostVerdict post_verdict(const PostArgs& a, int64_t row, const double* lds_row, double s,
-                                                    float pen_d) {
+// The row's verdict from the rule's (`rule`), its penalty and its sampled reward s: THE statement of the
+// penalized reward and of hard truncation (mopo_hip.h "Hard truncation") for the fused loops
+__device__ __forceinline__ PostVerdict post_conclude(const PostArgs& a, bool rule, float pen, double s) {
   PostVerdict v;
-  v.term = term_fn(a.term_kind, lds_row + 1, a.O);
-  v.pen = a.pen_dist ? pen_d : __uint_as_float(a.pen[row]);
-  v.pr = a.coeff != 0.f ? s - (double)a.coeff * (double)v.pen : s;
+  v.rule = rule;
+  v.pen = pen;
+  v.halted = a.halt && !(pen <= a.halt_threshold);               // u > threshold, or u is NaN
+  v.term = rule || v.halted;
+  v.pr = v.halted ? (double)a.halt_reward : (a.coeff != 0.f ? s - (double)a.coeff * (double)pen : s);
   return v;
 }
+__device__ __forceinline__ PostVerdict post_verdict(const PostArgs& a, int64_t row, const double* lds_row, double s,
+                                                    float pen_d) {
+  return post_conclude(a, term_fn(a.term_kind, lds_row + 1, a.O), a.pen_dist ? pen_d : __uint_as_float(a.pen[row]),
+                       s);
+}
+// a row's entry of a block's `kept` array: bit 0 the row goes on, bit 1 it was halted (0: not a live row)
+__device__ __forceinline__ int post_kept_word(const PostVerdict& v) { return (v.term ? 0 : 1) | (v.halted ? 2 : 0); }
 
-// With compaction: the kept rows of a block of ROWS rows from r0 on (PB % ROWS == 0), counted into the block's
-// PB-row chunk of blockcnt (zeroed before the launch)
+// The kept rows of a block of ROWS rows from r0 on (PB % ROWS == 0), counted into the block's PB-row chunk of
+// blockcnt (with compaction; zeroed before the launch), and its halted rows into *halted_cnt: at most one atomic
+// each per block.  Either pointer may be NULL.
 template <int ROWS>
-__device__ __forceinline__ void post_count_kept(const int* kept, int* blockcnt, int64_t r0) {
+__device__ __forceinline__ void post_count_kept(const int* kept, int* blockcnt, unsigned long long* halted_cnt,
+                                                int64_t r0) {
   __syncthreads();
   if (threadIdx.x == 0) {
-    int t = 0;
+    int t = 0, hl = 0;
 #pragma unroll
-    for (int i = 0; i < ROWS; ++i) t += kept[i];
-    if (t) atomicAdd(blockcnt + r0 / PB, t);
+    for (int i = 0; i < ROWS; ++i) { t += kept[i] & 1; hl += kept[i] >> 1; }
+    if (blockcnt && t) atomicAdd(blockcnt + r0 / PB, t);
+    if (halted_cnt && hl) atomicAdd(halted_cnt, (unsigned long long)hl);
   }
 }
 

@@ -182,7 +182,7 @@ __global__ __launch_bounds__(256) void rollout_val_post_kernel(const ValPostArgs
     if (live) a.keep[row] = keep ? 1 : 0;
     kept[rl] = keep ? 1 : 0;
   }
-  post_count_kept<POST_RPB>(kept, a.blockcnt, (int64_t)blockIdx.x * POST_RPB);
+  post_count_kept<POST_RPB>(kept, a.blockcnt, nullptr, (int64_t)blockIdx.x * POST_RPB);
 }
 
 // The statistics, one 256-thread workgroup per row of the table (rollout_eval_stats_kernel's scheme): row
@@ -342,6 +342,7 @@ extern "C" int mopo_rollout_validate(mopo_rollout_t hh, const mopo_rollout_args*
     ValPostArgs va{};
     va.p = rollout_post_args(h, a, m, i, oc, uc, 0, h->cnt, true);
     va.p.pool = *pool;
+    va.p.halt = 0; va.p.halted_cnt = nullptr;   // a segment ends where the data does: the halt fields are ignored
     va.uid_offset = a->uid_offset; va.B = B; va.start = h->val_start; va.k = i; va.K = K; va.t = t;
     if (rollout_zero_chunks(h, B, s)) return -1;
     hipLaunchKernelGGL(rollout_val_post_kernel, dim3(ceil_div((int)B, POST_RPB)), dim3(256), 0, s, va);

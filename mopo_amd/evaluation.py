@@ -108,6 +108,22 @@ def perf_metrics(evaluation, min_ret, max_ret):
 # The episodes run in FakeEnv, not in the task: the returns are returns UNDER THE MODEL, biased wherever the
 # model is wrong (the policy is trained to exploit exactly those places as far as the penalty lets it).  They
 # are no D4RL score, so no perf/NormalizedReturn is derived from them.
+def halt_threshold_from_quantile(u, q):
+    """The hard-truncation threshold at quantile ``q`` of the penalties ``u`` (``ModelRollout.penalty_profile``;
+    a tensor or an array): the order statistic ``sorted(u)[ceil(q * N) - 1]``, a value of ``u`` itself (no
+    interpolation), so exactly ``N - ceil(q * N)`` dataset rows lie above it when the values are distinct.
+    ``0 < q <= 1``; deterministic (``torch.sort``).  Returns a Python float."""
+    import math
+    import torch
+    if not 0.0 < float(q) <= 1.0:
+        raise ValueError('halt quantile must satisfy 0 < q <= 1 (got %r)' % (q,))
+    t = torch.as_tensor(u).reshape(-1)
+    n = int(t.numel())
+    if n == 0:
+        raise ValueError('halt quantile of an empty penalty profile')
+    return float(torch.sort(t)[0][int(math.ceil(float(q) * n)) - 1])
+
+
 MODEL_EVAL_KEYS = ('return-average', 'return-min', 'return-max', 'return-std', 'episode-length-avg',
                    'episode-length-min', 'episode-length-max', 'episode-length-std', 'penalized-return-average',
                    'penalty-average', 'terminated-fraction')

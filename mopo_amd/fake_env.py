@@ -12,7 +12,15 @@ numpy inputs return numpy outputs; torch CUDA inputs return torch CUDA outputs.
 
 ``penalty_kind`` (one of ``PENALTY_KINDS``; not in the reference) names the reward penalty; ``None`` keeps the
 reference's choice by ``penalty_learned_var``.  ``info['penalty']`` carries the selected kind's penalty.
+
+``halt_threshold`` / ``halt_reward`` (not in the reference; MOReL's HALT): a row whose penalty ``u`` of the selected
+kind is not ``<= halt_threshold`` is terminal and its penalized reward is exactly ``halt_reward``; every other
+output, and every row that does not halt, is what the step returns without them.  ``u`` is then computed whatever
+``penalty_coeff`` is.  ``halt_threshold=None``: off.
 """
+import math
+
+
 import numpy as np
 
 from . import _lib as L
@@ -45,10 +53,29 @@ def penalty_kind_id(penalty_kind=None, penalty_learned_var=None):
     return kind
 
 
+def halt_fields(halt_threshold=None, halt_reward=None):
+    """The C ABI's ``(halt, halt_threshold, halt_reward)`` of a hard-truncation choice.  A threshold of None is
+    off (a reward alone is ignored); a threshold without a reward, a NaN threshold or a reward that is not finite
+    raises ``ValueError``."""
+    if halt_threshold is None:
+        return 0, 0.0, 0.0
+    if halt_reward is None:
+        raise ValueError('halt_threshold=%r needs a halt_reward (the reward of a halted row, e.g. -100)'
+                         % (halt_threshold,))
+    thr, rew = float(halt_threshold), float(halt_reward)
+    if math.isnan(thr):
+        raise ValueError('halt_threshold must not be NaN')
+    if not math.isfinite(rew):
+        raise ValueError('halt_reward must be finite (got %r)' % (halt_reward,))
+    return 1, thr, rew
+
+
 class FakeEnv:
     def __init__(self, model, config, penalty_coeff=0., penalty_learned_var=False,
-                 penalty_learned_var_random=False, penalty_kind=None):
+                 penalty_learned_var_random=False, penalty_kind=None, halt_threshold=None, halt_reward=None):
         self.model = model
+        self._halt = halt_fields(halt_threshold, halt_reward)
+        self.halt_threshold, self.halt_reward = halt_threshold, halt_reward
         self.config = config
         self.penalty_coeff = penalty_coeff
         kind = penalty_kind_id(penalty_kind, penalty_learned_var)
@@ -112,7 +139,8 @@ class FakeEnv:
             term_kind=self.term_kind, d_next_obs=L.ptr(out['next_obs']), d_rewards=L.ptr(out['rew']),
             d_terminals=L.ptr(out['term']), d_penalty=L.ptr(out['penalty']), d_unpenalized=L.ptr(out['unpen']),
             d_info_mean=L.ptr(out['imean']), d_info_std=L.ptr(out['istd']), d_log_prob=L.ptr(out['logp']),
-            d_dev=L.ptr(out['dev']), d_ens_mean=L.ptr(out['emean']), d_ens_var=L.ptr(out['evar']))
+            d_dev=L.ptr(out['dev']), d_ens_mean=L.ptr(out['emean']), d_ens_var=L.ptr(out['evar']),
+            halt=self._halt[0], halt_threshold=self._halt[1], halt_reward=self._halt[2])
         L.check(L.lib().mopo_fakeenv_step(self.model.handle, args, L.stream_ptr(stream)))
         next_obs = out['next_obs']
         rew = out['rew'][:, None]

@@ -37,7 +37,8 @@ class MOPO:
                  n_epochs=1000, n_train_repeat=1, batch_size=256, seed=88, reparameterize=True, max_model_t=None,
                  rollout_random=False, evaluation_environment=None, eval_n_episodes=10, eval_deterministic=True,
                  max_path_length=1000, ensemble_dtype=None, actor_dtype=None, model_eval_episodes=0,
-                 model_eval_length=None, model_val_segments=0, model_val_horizon=None, penalty_kind=None, **kwargs):
+                 model_eval_length=None, model_val_segments=0, model_val_horizon=None, penalty_kind=None, halt_threshold=None,
+                 halt_quantile=None, halt_reward=None, **kwargs):
         """``ensemble_dtype``: the ensemble forward's arithmetic (``mopo_amd.bnn.DTYPES``), default
         ``DEFAULT_ENSEMBLE_DTYPE`` ('bf16x6': the f32 operands split exactly into 3 bf16 parts, 6 bf16
         MFMA products, f32 accumulate; 'fp32' above H = 256: ``bnn.default_ensemble_dtype``); 'fp32' runs
@@ -51,7 +52,20 @@ class MOPO:
         (``_validate_model``: ``model/open_loop/*`` diagnostics on every epoch's line); 0, the default, runs none.
         ``penalty_kind``: the reward penalty, one of ``fake_env.PENALTY_KINDS`` (None, the default: the
         reference's choice by ``penalty_learned_var``); the training rollouts, ``model_eval/*`` and
-        ``model/open_loop/*`` all use it."""
+        ``model/open_loop/*`` all use it.
+        ``halt_threshold`` / ``halt_quantile`` / ``halt_reward``: hard truncation (MOReL's HALT on the run's penalty
+        kind, ``fake_env.halt_fields``): a model transition whose penalty exceeds the threshold enters the model
+        pool terminal with the reward ``halt_reward`` and its rollout row stops there.  The threshold is given, or
+        resolved once, right after the ensemble is trained, as the ``halt_quantile`` order statistic of the penalty
+        over the whole env pool (``ModelRollout.penalty_profile``, ``evaluation.halt_threshold_from_quantile``);
+        giving both raises.  The training rollouts and ``model_eval/*`` use it, the open-loop validation does not;
+        every epoch's line carries ``model/halt-threshold``, ``model/halted-fraction`` (halted rows / rows added
+        by that epoch's rollouts) and, with model evaluation on, ``model_eval/halted-fraction``."""
+        from .config import check_halt_kwargs
+        check_halt_kwargs(dict(halt_threshold=halt_threshold, halt_quantile=halt_quantile, halt_reward=halt_reward))
+        self._halt_threshold = None if halt_threshold is None else float(halt_threshold)
+        self._halt_quantile, self._halt_reward = halt_quantile, halt_reward
+        self._epoch_rows = (0, 0)
         if kwargs.get('action_prior', 'uniform') != 'uniform':   # mopo.py:364 asserts the uniform prior
             raise AssertionError("MOPO's policy loss supports action_prior='uniform' only (mopo.py:364)")
         self._pool = pool                                   # device SimpleReplayPool of env data
@@ -143,12 +157,36 @@ class MOPO:
                                                 L.ptr(y), None))
         return self._model.train(x, y, permuted=True, **kwargs)
 
+    @property
+    def _halting(self):
+        return self._halt_threshold is not None or self._halt_quantile is not None
+
+    def _halt_modes(self):
+        """``halt_threshold`` / ``halt_reward`` of the rollout and evaluation calls ({}: no halting)."""
+        if not self._halting:
+            return {}
+        if self._halt_threshold is None:
+            raise RuntimeError('halt_quantile is resolved by train() after the ensemble is trained')
+        return dict(halt_threshold=self._halt_threshold, halt_reward=self._halt_reward)
+
+    def _resolve_halt(self):
+        """The halt threshold as a model-train metric ({}: no halting): given, or the ``halt_quantile`` order
+        statistic of the run's penalty kind over the whole env pool.  Reads the env pool and the model only."""
+        if not self._halting:
+            return {}
+        if self._halt_threshold is None:
+            from .evaluation import halt_threshold_from_quantile
+            ro = ModelRollout(self._model, min(max(self._pool.size, 1), 1 << 16), 1)
+            u = ro.penalty_profile(self._pool, self.fake_env.penalty_kind)
+            return {'halt-threshold': halt_threshold_from_quantile(u, self._halt_quantile)}
+        return {'halt-threshold': self._halt_threshold}
+
     # -- mopo.py:723-765 (device-resident, perf-mode RNG); ``deterministic`` as mopo.py:558-559 passes it
     def _rollout_model(self, rollout_batch_size, deterministic=None, rollout_key=None, **kwargs):
         key = self._epoch if rollout_key is None else rollout_key
         modes = dict(penalty_learned_var=self.fake_env.penalty_learned_var, penalty_kind=self.fake_env.penalty_kind,
                      deterministic=self._deterministic if deterministic is None else deterministic,
-                     rollout_random=self._rollout_random)
+                     rollout_random=self._rollout_random, **self._halt_modes())
         env_obs = self._pool.fields['observations'][:self._pool.size]
         if self._world > 1:
             return self._rollout_model_sharded(rollout_batch_size, env_obs, modes, key)
@@ -160,6 +198,9 @@ class MOPO:
                                   self._model._model_inds, seed=self._seed, epoch=key,
                                   pi_hidden=self._pi_hidden, actor_dtype=self._actor_dtype, **modes)
         added = int(steps.sum().item())
+        if self._halting:
+            self._epoch_rows = (self._epoch_rows[0] + int(self._rollout.last_halted.sum().item()),
+                                self._epoch_rows[1] + added)
         return {'mean_rollout_length': added / rollout_batch_size}
 
     def _rollout_model_sharded(self, rollout_batch_size, env_obs, modes, key):
@@ -179,6 +220,11 @@ class MOPO:
                                   epoch=key, pi_hidden=self._pi_hidden, actor_dtype=self._actor_dtype,
                                   **modes)
         added = int(steps.sum().item())
+        if self._halting:   # each rank counted its own shard's halted rows
+            import torch.distributed as dist
+            halted = self._rollout.ro.last_halted.sum()
+            dist.all_reduce(halted)
+            self._epoch_rows = (self._epoch_rows[0] + int(halted.item()), self._epoch_rows[1] + added)
         return {'mean_rollout_length': added / rollout_batch_size}
 
     # -- mopo.py:780-799 + 834-853: n steps of (_training_batch, _do_training, _update_target); the first
@@ -200,6 +246,7 @@ class MOPO:
         per_epoch = -(-self._epoch_length // f)
         metrics, logs = {}, {}
         t_roll = t_train = 0.0
+        self._epoch_rows = (0, 0)    # (halted rows, rows added) of this epoch's rollouts
         for k, ts in enumerate(range(0, self._epoch_length, f)):
             t0 = time.perf_counter()
             if self._real_ratio < 1.0:                                                  # mopo.py:554
@@ -219,6 +266,8 @@ class MOPO:
         diag = OrderedDict()
         diag.update(('evaluation/' + k, evaluation[k]) for k in sorted(evaluation))
         diag.update(('model/' + k, v) for k, v in metrics.items())
+        if self._halting:
+            diag['model/halted-fraction'] = self._epoch_rows[0] / max(self._epoch_rows[1], 1)
         diag.update(('training/' + k, v) for k, v in logs.items())
         diag.update({'Q_loss': (logs['Q/q1_loss'] + logs['sac_Q/q2_loss']) / 2, 'alpha': logs['sac_pi/alpha'],
                      'epoch': self._epoch, 'train-steps': self._num_train_steps,
@@ -268,8 +317,11 @@ class MOPO:
                                           pi_hidden=self._pi_hidden, actor_dtype=self._actor_dtype,
                                           penalty_learned_var=self.fake_env.penalty_learned_var,
                                           penalty_kind=self.fake_env.penalty_kind,
-                                          deterministic=self._deterministic)
-        return model_evaluation_metrics(out['stats'])
+                                          deterministic=self._deterministic, **self._halt_modes())
+        d = model_evaluation_metrics(out['stats'])
+        if self._halting:
+            d['halted-fraction'] = float(out['stats'][12])
+        return d
 
     # Philox key of the open-loop validation: bit 62 set as MODEL_EVAL_SEED_XOR's is (never a training key),
     # and another constant, so the two diagnostics never share a draw either.
@@ -302,6 +354,7 @@ class MOPO:
                 self._model_train_metrics = self._train_model(batch_size=256, max_epochs=max_epochs,
                                                               holdout_ratio=0.2, max_t=self._max_model_t)
                 self._model_train_metrics.update(self._validate_model())
+                self._model_train_metrics.update(self._resolve_halt())
             if self._world > 1:
                 from .distributed import broadcast_model, broadcast_numpy_rng, broadcast_metrics, wait_for_src
                 wait_for_src(self._wait_group)   # no RCCL collective is pending while rank 0 trains
@@ -309,6 +362,10 @@ class MOPO:
                 broadcast_numpy_rng()       # the training loop drew from numpy's global stream on rank 0 only
                 self._model_train_metrics = broadcast_metrics(self._model_train_metrics)
             self._model_train_metrics['train_time'] = time.perf_counter() - t0
+        if self._halting:
+            if 'halt-threshold' not in self._model_train_metrics:   # a model that was given, not trained here
+                self._model_train_metrics.update(self._resolve_halt())
+            self._halt_threshold = float(self._model_train_metrics['halt-threshold'])
         for self._epoch in range(self._epoch, n_epochs or self._n_epochs):
             d = self._train_epoch()
             d.update(('model/' + k, v) for k, v in self._model_train_metrics.items())
@@ -320,10 +377,11 @@ class MOPO:
 
 def from_config(params, pool, static_fns, model_load_dir=None, **overrides):
     """Build MOPO from ``mopo_amd.config.get_params(...)`` (examples/config/d4rl dicts)."""
-    from .config import DIMS, resolve_penalty_kind
+    from .config import DIMS, check_halt_kwargs, resolve_penalty_kind
     kw = dict(params['kwargs'])
     kw.update(overrides)
     resolve_penalty_kind(kw)
+    check_halt_kwargs(kw)
     obs_dim, act_dim = DIMS[params['domain']]
     kw.setdefault('model_load_dir', model_load_dir)
     return MOPO(pool, static_fns, obs_dim, act_dim, **kw)

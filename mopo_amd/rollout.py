@@ -119,8 +119,13 @@ class ModelRollout:
     def run(self, env_obs, pi_params, pool, batch_size, horizon, term_kind, penalty_coeff, elites,
             seed=0, epoch=0, pi_hidden=256, start_idx=None, eps_act=None, eps_obs=None, model_inds=None,
             staged=False, uid_offset=0, stream=None, step_desc=None, step_hook=None, penalty_learned_var=True,
-            deterministic=False, rollout_random=False, act_uniform=None, actor_dtype=None, penalty_kind=None):
+            deterministic=False, rollout_random=False, act_uniform=None, actor_dtype=None, penalty_kind=None,
+            halt_threshold=None, halt_reward=None):
         """Returns the device int64[horizon] tensor of rows added per step (steps_added).
+        ``halt_threshold`` / ``halt_reward``: hard truncation (``fake_env.halt_fields``; None: off) -- a row whose
+        penalty is not <= the threshold enters the pool terminal with the reward ``halt_reward`` and is dropped by
+        the compaction, which then runs for the never-done domains too; the rows halted per step are left in
+        ``self.last_halted`` (device int64[horizon]; None when off).
         ``step_desc(i)`` / ``step_hook(i, steps)``: per-step staging (see mopo_rollout_run_staged_steps).
         ``penalty_learned_var`` / ``deterministic``: FakeEnv's modes (fake_env.py:69-110; every D4RL
         config uses the learned-var penalty, not deterministic); ``rollout_random``: uniform actions
@@ -139,7 +144,13 @@ class ModelRollout:
         keep = [steps]
         args = self._args(keep, env_obs, pi_params, B, horizon, term_kind, penalty_coeff, elites, seed, epoch,
                           pi_hidden, start_idx, eps_act, eps_obs, model_inds, uid_offset, steps, penalty_learned_var,
-                          deterministic, rollout_random, act_uniform, actor_dtype, legacy, penalty_kind=penalty_kind)
+                          deterministic, rollout_random, act_uniform, actor_dtype, legacy, penalty_kind=penalty_kind,
+                          halt=(halt_threshold, halt_reward))
+        self.last_halted = None
+        if args.halt:
+            self.last_halted = torch.zeros(max(horizon, 1), dtype=torch.int64, device=dev)[:horizon]
+            keep.append(self.last_halted)
+            args.d_halted = L.ptr(self.last_halted)
         if step_hook is not None:
             # one call per horizon step into the staging block step_hook(i) names; step_hook(i, steps)
             # is then called after step i is enqueued (multi-GPU: gather step i while i + 1 computes)
@@ -157,10 +168,11 @@ class ModelRollout:
 
     def _args(self, keep, env_obs, pi_params, B, horizon, term_kind, penalty_coeff, elites, seed, epoch, pi_hidden,
               start_idx, eps_act, eps_obs, model_inds, uid_offset, steps, penalty_learned_var, deterministic,
-              rollout_random, act_uniform, actor_dtype, fresh_elites=False, penalty_kind=None):
+              rollout_random, act_uniform, actor_dtype, fresh_elites=False, penalty_kind=None, halt=(None, None)):
         """The C ABI's mopo_rollout_args; every tensor it points to is appended to ``keep``."""
         import torch
-        from .fake_env import penalty_kind_id
+        from .fake_env import halt_fields, penalty_kind_id
+        halt = halt_fields(*halt)
         # a named kind wins over run()'s default penalty_learned_var=True (only FakeEnv refuses a contradiction)
         kind = penalty_kind_id(penalty_kind, None if penalty_kind is not None else penalty_learned_var)
         dev = env_obs.device
@@ -186,19 +198,38 @@ class ModelRollout:
             d_model_inds=dptr(model_inds, torch.int32), d_steps=L.ptr(steps),
             penalty_learned_var=kind, deterministic=int(bool(deterministic)),
             rollout_random=int(bool(rollout_random)), d_act_uniform=dptr(act_uniform, torch.float32),
-            actor_dtype=_ACTOR_DTYPES[actor_dtype or default_actor_dtype(self.model.dtype)])
+            actor_dtype=_ACTOR_DTYPES[actor_dtype or default_actor_dtype(self.model.dtype)],
+            halt=halt[0], halt_threshold=halt[1], halt_reward=halt[2])
+
+    def penalty_profile(self, pool, kind, n_rows=None, stream=None):
+        """``u(observations[j], actions[j])`` of penalty ``kind`` (a name of ``fake_env.PENALTY_KINDS`` or its id)
+        for the first ``n_rows`` rows of ``pool`` (a ``SimpleReplayPool``, default: its ``size`` rows; or a
+        ``PoolDesc`` with ``n_rows`` given): a device f32[n_rows] tensor, computed in chunks of ``max_batch`` on
+        the current stream (csrc/penalty_profile.hip) -- the distribution a ``halt_threshold`` is calibrated on
+        (``evaluation.halt_threshold_from_quantile``).  Nothing is drawn; the pool is only read."""
+        import torch
+        from .fake_env import penalty_kind_id
+        desc = pool.desc() if not isinstance(pool, L.PoolDesc) else pool
+        dev = pool._state.device if hasattr(pool, '_state') else torch.device('cuda')
+        n = int(pool.size if n_rows is None else n_rows)
+        u = torch.empty(max(n, 0), dtype=torch.float32, device=dev)
+        L.check(L.lib().mopo_rollout_penalty_profile(self._h, desc, n, penalty_kind_id(kind), L.ptr(u),
+                                                     L.stream_ptr(stream)))
+        return u
 
     def evaluate(self, env_obs, pi_params, n_episodes, max_length, term_kind, penalty_coeff, elites,
                  policy_deterministic=True, seed=0, epoch=0, pi_hidden=256, start_idx=None, eps_act=None,
                  eps_obs=None, model_inds=None, uid_offset=0, stream=None, penalty_learned_var=True,
-                 deterministic=False, rollout_random=False, act_uniform=None, actor_dtype=None, penalty_kind=None):
+                 deterministic=False, rollout_random=False, act_uniform=None, actor_dtype=None, penalty_kind=None,
+                 halt_threshold=None, halt_reward=None):
         """Model-based policy evaluation (csrc/rollout_eval.hip): ``n_episodes`` episodes of at most
         ``max_length`` <= 4095 steps of the policy inside the learned model, from env-pool start states, on the
         current stream; nothing enters a pool and numpy's global stream is not drawn from.
         ``policy_deterministic``: tanh(mu) actions (the evaluation policy, mopo.py:481-482), else sampled --
         then the episodes are the trajectories ``run`` visits for the same arguments.  The other arguments
         are ``run``'s; the penalty sums and penalized returns are of the selected ``penalty_kind``.  Returns device tensors: ``returns`` (unpenalized), ``penalized_returns``,
-        ``penalty_sums`` (f64[n]), ``lengths`` (i32[n]), ``terminated`` (u8[n]), ``steps`` (int64[max_length] live
+        ``penalty_sums`` (f64[n]), ``lengths`` (i32[n]), ``terminated`` (u8[n]; ended by the termination rule), ``halted`` (u8[n]; ended by ``halt_threshold`` /
+        ``halt_reward``, ``run``'s hard truncation -- zeros when off), ``steps`` (int64[max_length] live
         episodes per step) and ``stats`` (f64[16], see ``evaluation.model_evaluation_metrics``).  These are
         returns under the model: biased wherever the model is wrong."""
         import torch
@@ -209,16 +240,18 @@ class ModelRollout:
                'penalty_sums': torch.zeros(n, dtype=torch.float64, device=dev),
                'lengths': torch.zeros(n, dtype=torch.int32, device=dev),
                'terminated': torch.zeros(n, dtype=torch.uint8, device=dev),
+               'halted': torch.zeros(n, dtype=torch.uint8, device=dev),
                'steps': torch.zeros(max(T, 1), dtype=torch.int64, device=dev),
                'stats': torch.zeros(16, dtype=torch.float64, device=dev)}
         keep = list(out.values())
         args = self._args(keep, env_obs, pi_params, n, T, term_kind, penalty_coeff, elites, seed, epoch, pi_hidden,
                           start_idx, eps_act, eps_obs, model_inds, uid_offset, out['steps'], penalty_learned_var,
-                          deterministic, rollout_random, act_uniform, actor_dtype, penalty_kind=penalty_kind)
+                          deterministic, rollout_random, act_uniform, actor_dtype, penalty_kind=penalty_kind,
+                          halt=(halt_threshold, halt_reward))
         ev = L.EvalArgs(policy_deterministic=int(bool(policy_deterministic)), d_return=L.ptr(out['returns']),
                         d_pen_return=L.ptr(out['penalized_returns']), d_pen_sum=L.ptr(out['penalty_sums']),
                         d_length=L.ptr(out['lengths']), d_terminated=L.ptr(out['terminated']),
-                        d_stats=L.ptr(out['stats']))
+                        d_stats=L.ptr(out['stats']), d_halted=L.ptr(out['halted']))
         L.check(L.lib().mopo_rollout_evaluate(self._h, args, ev, L.stream_ptr(stream)))
         self._keepalive = keep
         return out

@@ -12,6 +12,8 @@ epoch (``model_eval/*``: the return under the model, not a D4RL score); off by d
 ``--model-val-segments`` / ``--model-val-horizon``: replay dataset trajectories open-loop through the trained
 model (``model/open_loop/*``: the compounding error and the penalty's calibration); off by default.
 ``--penalty-kind``: the reward penalty (mopo_amd.fake_env.PENALTY_KINDS); default: the config's choice.
+``--halt-threshold`` or ``--halt-quantile``, with ``--halt-reward``: hard truncation of the model rollouts where
+the penalty exceeds the threshold (given, or that quantile of the penalty over the dataset); off by default.
 """
 import argparse
 import json
@@ -45,6 +47,11 @@ def main(argv=None):
     p.add_argument('--penalty-kind', default=None, choices=PENALTY_KINDS,
                    help='the reward penalty u of r - penalty_coeff * u (default: the config kwarg penalty_kind, else '
                         'by its penalty_learned_var: max_aleatoric / mean_distance)')
+    p.add_argument('--halt-threshold', type=float, default=None,
+                   help='hard truncation: a model transition whose penalty exceeds this is terminal with --halt-reward')
+    p.add_argument('--halt-quantile', type=float, default=None,
+                   help='... the threshold as this quantile (0 < q <= 1) of the penalty over the dataset instead')
+    p.add_argument('--halt-reward', type=float, default=None, help='the reward of a halted transition, e.g. -100')
     a = p.parse_args(argv)
     from .config import DIMS, get_params
     from .loader import restore_pool
@@ -60,7 +67,9 @@ def main(argv=None):
     over.update((k, v) for k, v in (('model_eval_episodes', a.model_eval_episodes),
                                     ('model_eval_length', a.model_eval_length),
                                     ('model_val_segments', a.model_val_segments),
-                                    ('model_val_horizon', a.model_val_horizon)) if v is not None)
+                                    ('model_val_horizon', a.model_val_horizon),
+                                    ('halt_threshold', a.halt_threshold), ('halt_quantile', a.halt_quantile),
+                                    ('halt_reward', a.halt_reward)) if v is not None)
     algo = from_config(params, pool, static_fns[params['domain']], model_load_dir=a.model_dir, seed=a.seed, **over)
     for diag in algo.train(a.epochs):
         print(json.dumps({k: float(v) for k, v in diag.items()}), flush=True)
