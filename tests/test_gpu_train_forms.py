@@ -10,8 +10,8 @@ that fill their last 16-block (or half of it), E = 3 / 7, and one shape of the g
   d  the generic grouped-GEMM step: widths without a row form, odd D, H % 4 != 0, K > 256, more than 8 members
      (a backward launch's two problems per member then exceed one grouped launch: step_impl once refused them);
   e  single-row minibatches;
-  f  a and b again with MOPO_TRAIN_ROWS=0 (every shape on the generic path), without and with
-     MOPO_TRAIN_WGRAD_TILE=16;
+  f  a and b again with MOPO_TRAIN_ROWS=0 (every shape on the generic path), without and with a
+     retired knob that the library no longer reads;
   g  mopo_bnn_train_logs against the oracle's loss;  h  mopo_bnn_train_eval_mse;  i  snapshot / restore.
 Each parity case first asks mopo_bnn_train_step_form which path its shape takes in this process, so a case
 written for a row form cannot pass on the generic path unnoticed, and prints that form with its worst d / tol.
@@ -164,10 +164,9 @@ def test_num_networks_outside_1_16_is_refused(E):
 @pytest.mark.parametrize('knobs', ['MOPO_TRAIN_ROWS=0', 'MOPO_TRAIN_ROWS=0,MOPO_TRAIN_WGRAD_TILE=16'])
 def test_generic_path_knobs_match_oracle(knobs):
     """MOPO_TRAIN_ROWS=0 sends every shape of groups a and b down the generic path (twelve grouped-GEMM launches).
-    MOPO_TRAIN_WGRAD_TILE is read by the unfused row path's weight-gradient launch alone, which a default build
-    (MOPO_TRAIN_FUSED=1) compiles but never reaches: setting it must change nothing.  Both are read once per
-    process, so each setting runs the two groups in a fresh process, where the step-form assertion expects the
-    generic path."""
+    MOPO_TRAIN_WGRAD_TILE was read by a three-launch row path that no build could reach and that has been removed;
+    nothing reads it now, so setting it must change nothing.  MOPO_TRAIN_ROWS is read once per process, so each
+    setting runs the two groups in a fresh process, where the step-form assertion expects the generic path."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
