@@ -106,8 +106,10 @@ def q_backward(Q, c, dq, need_params=True):
     return grads, dx
 
 
-def pi_backward(P, c, dlogp, da):
-    """Backprop d(logp) [n] and d(a) [n,A] (a = tanh(u)) to pi params."""
+def pi_backward(P, c, dlogp, da, mask='both'):
+    """Backprop d(logp) [n] and d(a) [n,A] (a = tanh(u)) to pi params.  ``mask``: which sides of the log-std
+    clip stop the gradient -- 'both' is clip_by_value's rule; 'none', 'lower' and 'upper' restate it broken
+    (tests/sac_cases.py measures that a case can tell them apart)."""
     W1, b1, W2, b2, Wm, bm, Wl, bl = P
     u, mu, std, ls, zz, eps = c['u'], c['mu'], c['std'], c['ls'], c['zz'], c['eps']
     g = dlogp[:, None]
@@ -122,7 +124,9 @@ def pi_backward(P, c, dlogp, da):
     dstd = dstd + du * eps
     dls = dls + dstd * std                                          # std = exp(ls)
     r = c['ls_raw']
-    dls_raw = dls * ((r >= LOG_STD_MIN) & (r <= LOG_STD_MAX))       # clip_by_value grad
+    keep = (r >= LOG_STD_MIN) | (mask not in ('both', 'lower'))
+    keep = keep & ((r <= LOG_STD_MAX) | (mask not in ('both', 'upper')))
+    dls_raw = dls * keep                                            # clip_by_value grad
     gWm = c['h2'].T @ dmu; gbm = dmu.sum(0)
     gWl = c['h2'].T @ dls_raw; gbl = dls_raw.sum(0)
     dh2 = dmu @ Wm.T + dls_raw @ Wl.T
@@ -175,12 +179,12 @@ def prior_log_prob(a):
 
 
 def sac_step(st, batch, eps_s, eps_s2, gamma=0.99, tau=5e-3, reward_scale=1.0, target_entropy=-3.0, grads_out=None,
-             action_prior='uniform'):
+             action_prior='uniform', clip_mask='both'):
     """One ``_do_training`` + ``_update_target`` (mopo.py:834-853). Mutates ``st``; returns logs.
     ``grads_out`` (dict): receives the pre-step gradients 'pi', 'q1', 'q2' (lists) and 'alpha'.
     ``action_prior='normal'``: softlearning's SAC (sac.py:285-289, 304-306) subtracts the standard-normal
     log-prob of the policy's action from the policy loss (MOPO's own graph asserts 'uniform',
-    mopo.py:364)."""
+    mopo.py:364).  ``clip_mask``: pi_backward's ``mask``."""
     s, a, s2 = batch['observations'], batch['actions'], batch['next_observations']
     r, d = batch['rewards'][:, 0], batch['terminals'][:, 0].astype(st.dtype)
     n = s.shape[0]
@@ -211,7 +215,7 @@ def sac_step(st, batch, eps_s, eps_s2, gamma=0.99, tau=5e-3, reward_scale=1.0, t
     da = dx1[:, O:] + dx2[:, O:]
     if action_prior == 'normal':
         da = da + a_pi / n                                          # d/da of -mean(log N(a; 0, I))
-    g_pi = pi_backward(P, cpi, np.full(n, alpha / n, st.dtype), da)
+    g_pi = pi_backward(P, cpi, np.full(n, alpha / n, st.dtype), da, mask=clip_mask)
     g_alpha = -np.mean(logp_pi + target_entropy)                    # d/dlog_alpha of :437-438
     if grads_out is not None:
         grads_out.update(pi=g_pi, q1=g_q1, q2=g_q2, alpha=g_alpha)

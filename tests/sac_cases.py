@@ -12,13 +12,19 @@ obs_dim <= 31, act_dim <= 8 and any n_env in [0, batch].  The groups:
   D  perf-mode steps under graph replay against the oracle run on the restated streams (oracle/rng.py),
      among them the shapes with a single B1 block (H <= 64 and batch <= 16), whose prefetch is its own launch;
   E  the launch forms (MOPO_SAC_FUSE 0 / 1 / 2, graph replay against eager steps): bit-identity, no oracle;
-  F  refusals (REFUSALS below).
+  F  refusals (REFUSALS below);
+  G  saturated policy heads (``Case.head``, HEAD_MODES): the log-std clip's clamped branches and its gradient
+     mask, which no other group reaches (their raw log-std lies in [-1.97, 1.90]).  Injected steps, one
+     perf-mode case, and a copy of that in group E.  Where a raw log-std is below the lower bound the
+     injected noise is exactly 0: std = e^-20 is below EPS and below half an ulp of mu, so with noise
+     u - mu is 0 or +-1 ulp in f32 and zz / (std + EPS) amplifies that by 1e8 in the oracle as in any kernel.
 
 The tolerances are the project's own (tests/test_gpu_sac.py's docstring and its non-square perf-mode test);
 the *_ratio functions express a comparison in units of its tolerance, so that 1.0 is the GPU bound and the
 CPU conditioning test can ask for CONDITION of it.
 """
 import collections
+import contextlib
 import functools
 
 import numpy as np
@@ -39,11 +45,27 @@ LOG_PAIRS = [(k, k) for k in ('Q/q1_loss', 'sac_Q/q2_loss', 'sac_Q/q1', 'sac_Q/q
 LOSS_PAIRS = [('Q/q1_loss', 'Q/q1_loss'), ('sac_Q/q2_loss', 'sac_Q/q2_loss'), ('policy_loss', 'pi_loss')]
 
 # seed: the data seed (pools, parameters, injected rows and noise); steps: perf-mode steps (0: one injected step)
-Case = collections.namedtuple('Case', 'group o a hidden n n_env seed prior steps')
+# head: how the log-std head is saturated ('' : as initialised; HEAD_MODES)
+Case = collections.namedtuple('Case', 'group o a hidden n n_env seed prior steps head')
+
+# The log-std head's columns by class: +1 above the upper bound on every row (bl += HEAD_UP), -1 below the lower
+# one (bl -= HEAD_DOWN), 0 inside as initialised.  'cross' shifts no whole column: cross_head() makes column
+# CROSS_COL lie above the bound on some rows and inside on the others.
+HEAD_MODES = {
+    'upper': lambda j: 1 + 0 * j,
+    'lower': lambda j: -1 + 0 * j,
+    'mixed': lambda j: np.where(j % 3 == 0, 1, np.where(j % 3 == 1, -1, 0)),   # dim_cases.SATURATED_SHAPES' scheme
+    'even': lambda j: np.where(j % 2 == 0, 1, 0),
+    'cross': lambda j: 0 * j,
+}
+HEAD_UP, HEAD_DOWN = 6.0, 26.0
+CROSS_COL = 4                                  # of the six, the column whose raw value separates the clusters best
+CLIP_MARGIN = 0.5                              # every raw log-std of a G case lies this far from both bounds
+INSIDE = 2.0                                   # 'cross': the rows that stay inside stay above -INSIDE
 
 
-def _c(group, o, a, hidden, n, n_env=None, seed=0, prior='uniform', steps=0):
-    return Case(group, o, a, hidden, n, int(n * 0.05) if n_env is None else n_env, seed, prior, steps)
+def _c(group, o, a, hidden, n, n_env=None, seed=0, prior='uniform', steps=0, head=''):
+    return Case(group, o, a, hidden, n, int(n * 0.05) if n_env is None else n_env, seed, prior, steps, head)
 
 
 CASES = [
@@ -99,6 +121,19 @@ CASES = [
     _c('E', 17, 6, 256, 1024),
     _c('E', 27, 8, 240, 1000),
     _c('E', 11, 3, 80, 528),
+    _c('E', 17, 6, 64, 40, head='even'),   # G's perf-mode case under the launch forms and graph replay
+    # G. saturated heads: one injected step; lower-clipped entries carry zero noise
+    _c('G', 3, 1, 16, 17, head='upper'),               # A = 1, one B1 block
+    _c('G', 3, 1, 16, 17, head='lower'),
+    _c('G', 11, 3, 64, 40, head='mixed'),
+    _c('G', 17, 6, 256, 100, head='mixed'),
+    _c('G', 17, 6, 256, 100, head='cross'),            # the mask is per element, not per column
+    # wide layer 1.  seed 0: fp32 rounds the Polyak average of one unmoved bl entry near -26 by an ulp (1.9e-6),
+    # 0.65 of the target tolerance; without the head shifts the same shape and seed sit at 0.009
+    _c('G', 27, 8, 96, 40, seed=1, prior='normal', head='mixed'),
+    _c('G', 17, 6, 256, 513, head='mixed'),            # three K passes: sac_wgrad.h recomputes the clamp per chunk
+    _c('G', 11, 3, (48, 200), 100, head='mixed'),      # zero-padded widths
+    _c('G', 17, 6, 64, 40, steps=3, head='even'),      # perf mode: the upper clip and the inside class only
 ]
 
 # F. refusals: (constructor keywords over SAC(11, 3, ...), a pattern of the message)
@@ -125,7 +160,7 @@ def hidden_id(hidden):
 
 def case_id(c):
     s = '%s-%d+%d-%s-n%d-e%d' % (c.group, c.o, c.a, hidden_id(c.hidden), c.n, c.n_env)
-    return s + ('-normal' if c.prior == 'normal' else '')
+    return s + ('-normal' if c.prior == 'normal' else '') + ('-' + c.head if c.head else '')
 
 
 def real_ratio(c):
@@ -171,14 +206,64 @@ def case_inputs(c):
         mod = nan_pool(c.o, c.a)
     params = [(p + rs.normal(size=p.shape) * 0.02).astype(np.float32)      # non-zero biases
               for p in osac.init_params(c.o, c.a, c.hidden, seed=9)]
+    if c.head == 'cross':
+        cross_head(c, env, mod, params)
+    elif c.head:
+        cls = head_classes(c)
+        params[7] = (params[7] + np.where(cls > 0, HEAD_UP, np.where(cls < 0, -HEAD_DOWN, 0.0))).astype(np.float32)
     ne, nm = len(env['rewards']), len(mod['rewards'])
     if c.steps:
+        assert not c.head or (head_classes(c) >= 0).all(), 'the lower clip needs injected (zeroed) noise'
         idx, e1, e2 = perf_streams(c, ne, nm, 0)
     else:
         idx = np.concatenate([rs.randint(0, ne, c.n_env), rs.randint(0, nm, c.n - c.n_env)]).astype(np.int64)
         e1 = rs.normal(size=(c.n, c.a)).astype(np.float32)
         e2 = rs.normal(size=(c.n, c.a)).astype(np.float32)
-    return dict(case=c, env=env, mod=mod, params=params, log_alpha=np.float32(LOG_ALPHA), idx=idx, eps_s=e1, eps_n=e2)
+    ci = dict(case=c, env=env, mod=mod, params=params, log_alpha=np.float32(LOG_ALPHA), idx=idx, eps_s=e1, eps_n=e2)
+    if c.head and (head_classes(c) < 0).any():
+        # no noise where the fp64 oracle's raw log-std is below the lower bound: u == mu in every precision
+        raw = head_raw(params, host_batch(ci, idx, np.float64))
+        e1[raw[0] < osac.LOG_STD_MIN] = 0
+        e2[raw[1] < osac.LOG_STD_MIN] = 0
+    return ci
+
+
+def head_classes(c):
+    """Per column of the log-std head: +1 shifted above the upper bound, -1 below the lower one, 0 left alone."""
+    return np.asarray(HEAD_MODES[c.head](np.arange(c.a)))
+
+
+def head_raw(params, batch):
+    """The raw (unclipped) log-std of pi(s) and pi(s') on ``batch`` [2, n, a], in the parameters' precision."""
+    P = [np.asarray(p, batch['observations'].dtype) for p in params[:8]]
+    z = np.zeros((len(batch['observations']), P[7].size), batch['observations'].dtype)
+    return np.stack([osac.pi_forward(P, batch[k], z)[4]['ls_raw'] for k in ('observations', 'next_observations')])
+
+
+def cross_head(c, env, mod, params):
+    """'cross': observations in two clusters (an eighth of their spread around two centres), then column CROSS_COL
+    of Wl times a power of two and its bias shifted, so that on every pool row -- pi(s) and pi(s') alike -- the
+    column's raw log-std is either above the upper bound or inside, above -INSIDE, at least 0.2 further from the
+    bound than CLIP_MARGIN.  Which side a row falls on is its cluster's; every change is exact in f32."""
+    rs = np.random.RandomState(5000 + c.seed)
+    centres = rs.normal(size=(2, c.o))
+    for pool in (env, mod):
+        for k in ('observations', 'next_observations'):
+            z = rs.randint(0, 2, len(pool[k]))
+            pool[k] = (0.125 * pool[k] + centres[z]).astype(np.float32)
+    f = np.float64
+    both = {k: np.concatenate([env[k], mod[k]]).astype(f) for k in ('observations', 'next_observations')}
+    v = head_raw([p.astype(f) for p in params], both)[:, :, CROSS_COL].ravel()
+    cut = 0.5 * (v.min() + v.max())
+    lo, hi = v[v < cut], v[v >= cut]
+    gap, width = hi.min() - lo.max(), lo.max() - lo.min()
+    m = CLIP_MARGIN + 0.2
+    k = 2.0 ** np.ceil(np.log2(2 * m / gap))
+    assert gap > 0 and k * width <= osac.LOG_STD_MAX - m + INSIDE - 0.2, (gap, width, k)
+    params[6] = params[6].copy()
+    params[6][:, CROSS_COL] *= np.float32(k)
+    params[7] = params[7].copy()
+    params[7][CROSS_COL] = np.float32(k * params[7][CROSS_COL] + (osac.LOG_STD_MAX - m - k * lo.max()))
 
 
 def perf_streams(c, env_size, model_size, k, seed=PERF_SEED):
@@ -224,21 +309,55 @@ def _margins(st, batch, e1):
     return float(np.abs(q1 - q2).min()), float(max(np.abs(q1).max(), np.abs(q2).max())), float(clip)
 
 
-def oracle_step(ci, dtype=np.float64):
+# The clip rule restated broken, for the sensitivity measurement of group G: name -> (keywords of broken_rule,
+# the class of entries the break shows on: +1 upper, -1 lower, 0 either)
+BREAKS = {
+    'no clamp': (dict(lo=-np.inf, hi=np.inf), 0),
+    'upper bound 2.5': (dict(hi=2.5), 1), 'upper bound 1.5': (dict(hi=1.5), 1),
+    'lower bound -19.5': (dict(lo=-19.5), -1), 'lower bound -20.5': (dict(lo=-20.5), -1),
+    'no mask': (dict(mask='none'), 0),
+    'mask below only': (dict(mask='lower'), 1), 'mask above only': (dict(mask='upper'), -1),
+}
+
+
+def breaks_of(c):
+    """The BREAKS that a case's classes can show ('cross' has upper entries)."""
+    cls = set(head_classes(c).tolist()) | ({1} if c.head == 'cross' else set())
+    return [k for k, (_, side) in BREAKS.items() if side == 0 or side in cls]
+
+
+@contextlib.contextmanager
+def broken_rule(lo=osac.LOG_STD_MIN, hi=osac.LOG_STD_MAX, mask='both'):
+    """oracle/sac.py with other clip bounds (its module constants) for the length of the block; yields the
+    ``clip_mask`` keyword of sac_step."""
+    keep = osac.LOG_STD_MIN, osac.LOG_STD_MAX
+    osac.LOG_STD_MIN, osac.LOG_STD_MAX = lo, hi
+    try:
+        with np.errstate(over='ignore'):       # an unclamped std of e^8 overflows sigmoid's exp to the right limit
+            yield dict(clip_mask=mask)
+    finally:
+        osac.LOG_STD_MIN, osac.LOG_STD_MAX = keep
+
+
+def oracle_step(ci, dtype=np.float64, rule=None):
     """One step of oracle/sac.py on the case's first batch, run in ``dtype``: dict with the pre-step ``grads``
     (the 20 tensors), ``g_alpha``, ``logs``, the state after the step (``params`` / ``target`` / ``adam_m`` /
-    ``adam_v`` flat, log_alpha last where SAC.state_dict() has it) and ``margins`` (_margins)."""
+    ``adam_v`` flat, log_alpha last where SAC.state_dict() has it), ``margins`` (_margins) and ``ls_raw``
+    (head_raw).  ``rule``: keywords of broken_rule, the step under a broken clip rule."""
     c = ci['case']
     dtype = np.dtype(dtype)
     st = _state(ci, dtype)
     batch = host_batch(ci, ci['idx'], dtype)
     e1, e2 = ci['eps_s'].astype(dtype), ci['eps_n'].astype(dtype)
     margins = _margins(st, batch, e1)
+    raw = head_raw(st.params, batch)
     got = {}
-    logs = osac.sac_step(st, batch, e1, e2, target_entropy=TARGET_ENTROPY, grads_out=got, action_prior=c.prior)
+    with broken_rule(**(rule or {})) as kw:
+        logs = osac.sac_step(st, batch, e1, e2, target_entropy=TARGET_ENTROPY, grads_out=got, action_prior=c.prior, **kw)
     out = dict(grads=got['pi'] + got['q1'] + got['q2'], g_alpha=got['alpha'], logs=logs, **_snapshot(st))
     _assert_dtype(out, dtype)        # an fp32 run that picked up an fp64 constant would flatter the case
     out['margins'] = margins
+    out['ls_raw'] = raw
     return out
 
 
@@ -250,16 +369,36 @@ def oracle_steps(c, K=None, seed=PERF_SEED, dtype=np.float64):
     ci = case_inputs(c)
     st = _state(ci, dtype)
     ne, nm = len(ci['env']['rewards']), len(ci['mod']['rewards'])
-    rows = []
+    rows, raws = [], []
     for k in range(c.steps if K is None else K):
         idx, e1, e2 = perf_streams(c, ne, nm, k, seed)
-        logs = osac.sac_step(st, host_batch(ci, idx, dtype), e1.astype(dtype), e2.astype(dtype),
+        batch = host_batch(ci, idx, dtype)
+        raws.append(head_raw(st.params, batch))
+        logs = osac.sac_step(st, batch, e1.astype(dtype), e2.astype(dtype),
                              target_entropy=TARGET_ENTROPY, action_prior=c.prior)
         rows.append(idx)
     out = dict(logs=logs, **_snapshot(st))
     _assert_dtype(out, dtype)
     out['idx'] = np.stack(rows)
+    out['ls_raw'] = np.stack(raws)         # [K, 2, n, a]: each step's raw log-std of pi(s), pi(s'), pre-step
     return out
+
+
+def clipped_columns(ls_raw):
+    """The head columns whose raw log-std of pi(s) is outside the clip bounds on every row of ``ls_raw``
+    ([..., n, a]): their Wl column and bl entry get exactly no gradient."""
+    r = np.asarray(ls_raw).reshape(-1, np.asarray(ls_raw).shape[-1])
+    return np.flatnonzero(((r < osac.LOG_STD_MIN) | (r > osac.LOG_STD_MAX)).all(0))
+
+
+def head_column_index(c, cols):
+    """Where column j of pi.Wl and entry j of pi.bl (j in ``cols``) lie in the flat [H1, H2] parameter layout
+    (the same offsets in the gradients and, the four optimizers laid out pi, q1, q2, alpha, the Adam slots)."""
+    sizes = [int(np.prod(s)) for s in osac.PI_SHAPES(c.o, c.a, c.hidden)]
+    off = sum(sizes[:6])
+    h2 = osac._hs(c.hidden)[1]
+    wl = [off + np.arange(h2) * c.a + j for j in cols]
+    return np.concatenate(wl + [off + sizes[6] + np.asarray(cols, np.int64)]).astype(np.int64)
 
 
 @functools.lru_cache(maxsize=None)

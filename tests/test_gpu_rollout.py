@@ -150,11 +150,13 @@ def test_pool_vs_reference_trace():
 
 
 def _rollout_case(domain, E, H, B, horizon, seed, coeff=1.0, O=17, A=6, height=None, learned_var=True, det=False,
-                  rand_act=False):
+                  rand_act=False, policy=None):
     """Oracle rollout with every random stream drawn in the reference order; returns inputs,
     injected streams and the oracle pool.  ``height``: fixed walker height (50: every row done).
     ``learned_var`` / ``det``: FakeEnv's penalty and deterministic modes (fake_env.py:69-110);
-    ``rand_act``: rollout_random (mopo.py:736-738: uniform actions drawn after get_action_meta)."""
+    ``rand_act``: rollout_random (mopo.py:736-738: uniform actions drawn after get_action_meta);
+    ``policy``: a function (flat, O, A) -> (flat, factor [A]) that restates the 256-wide policy and scales the
+    policy noise per action column (tests/actor_regimes.py rollout_policy)."""
     rs = np.random.RandomState(seed)
     env_n = 3000
     env_obs = rs.normal(size=(env_n, O)).astype(np.float32)
@@ -170,6 +172,9 @@ def _rollout_case(domain, E, H, B, horizon, seed, coeff=1.0, O=17, A=6, height=N
     p = obnn.from_mat_list(mats)
     # keep the model's predicted change small so walker rows terminate at a moderate rate
     flat = __import__('mopo_amd.rollout', fromlist=['x']).init_sac_params(O, A, 256, seed=seed + 2)
+    eps_factor = np.ones(A, np.float32)
+    if policy is not None:
+        flat, eps_factor = policy(flat, O, A)
     P = [q.astype(np.float64) for q in __import__('mopo_amd.rollout', fromlist=['x']).split_params(flat, O, A)[:8]]
     elites = [4, 1, 0, 6, 2][:min(5, E)]
     env_pool = opool.Pool(O, A, env_n)
@@ -187,7 +192,7 @@ def _rollout_case(domain, E, H, B, horizon, seed, coeff=1.0, O=17, A=6, height=N
     steps = []
     for i in range(horizon):
         Bi = len(obs)
-        ea = act_rs.normal(size=(Bi, A)).astype(np.float32)
+        ea = act_rs.normal(size=(Bi, A)).astype(np.float32) * eps_factor
         act, _ = osac.actor_act(P, obs.astype(np.float32).astype(np.float64), ea.astype(np.float64))
         act = act.astype(np.float32)
         if rand_act:

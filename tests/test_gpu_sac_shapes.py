@@ -69,10 +69,33 @@ def report(case, ratios, extra=''):
     assert not bad, (sc.case_id(case), bad)
 
 
-@pytest.mark.parametrize('case', sc.by_group('A', 'B'), ids=sc.case_id)
+def assert_clipped_columns_stand_still(case, ci, ls_raw, got, grads=None):
+    """The head columns whose raw log-std is clipped on every row of every step: no gradient reaches their
+    pi.Wl column and pi.bl entry (clip_by_value's mask), exactly -- the gradient and both Adam slots are 0 and
+    the parameters keep their bits, as in the oracle."""
+    cols = sc.clipped_columns(ls_raw)
+    want = np.flatnonzero(sc.head_classes(case) != 0)
+    np.testing.assert_array_equal(cols, want)
+    if not len(cols):
+        return
+    at = sc.head_column_index(case, cols)
+    assert len(at) == len(cols) * (sc.osac._hs(case.hidden)[1] + 1)
+    for name, v in (('gradient', grads), ('adam_m', got['adam_m']), ('adam_v', got['adam_v'])):
+        if v is not None:
+            assert np.all(np.asarray(v)[at] == 0), (name, np.abs(np.asarray(v)[at]).max())
+    before = sc.flat(ci['params'])
+    assert before.dtype == got['params'].dtype == np.float32
+    np.testing.assert_array_equal(got['params'][at].view(np.uint32), before[at].view(np.uint32))
+    moved = np.ones(before.size, bool)
+    moved[at] = False
+    assert (got['params'][:-1][moved] != before[moved]).mean() > 0.5          # ... while most of the rest moved
+
+
+@pytest.mark.parametrize('case', [c for c in sc.by_group('A', 'B', 'G') if not c.steps], ids=sc.case_id)
 def test_one_injected_step_vs_oracle(case):
-    """Groups A, B: one step on injected rows and noise; logs, every gradient and the alpha gradient, the
-    parameters, Adam slots and targets after the step."""
+    """Groups A, B, G: one step on injected rows and noise; logs, every gradient and the alpha gradient, the
+    parameters, Adam slots and targets after the step.  G: the heads are saturated (sac_cases.py), and what
+    the gradient mask must leave untouched is untouched exactly."""
     ci, ref = sc.reference_step(case)
     env_p, mod_p = device_pools(ci)
     sac = make_sac(ci)
@@ -83,11 +106,13 @@ def test_one_injected_step_vs_oracle(case):
     report(case, sc.step_ratios(got, ref))
     if not np.isscalar(case.hidden):
         assert_padding_zero(sac)
+    if case.head:
+        assert_clipped_columns_stand_still(case, ci, ref['ls_raw'][0], got, got['grads'][0])
 
 
-@pytest.mark.parametrize('case', sc.by_group('C', 'D'), ids=sc.case_id)
+@pytest.mark.parametrize('case', [c for c in sc.by_group('C', 'D', 'G') if c.steps], ids=sc.case_id)
 def test_perf_mode_steps_vs_oracle(case):
-    """Groups C, D: perf-mode steps under graph replay (device Philox rows and noise) against the oracle on
+    """Groups C, D, G: perf-mode steps under graph replay (device Philox rows and noise) against the oracle on
     the restated streams.  The handle does not expose the rows it sampled; a wrong row shows in every
     compared quantity, and a read of the unused NaN pool (n_env = 0, n_env = n) in all of them at once."""
     ref = sc.reference_steps(case)
@@ -100,6 +125,8 @@ def test_perf_mode_steps_vs_oracle(case):
     report(case, sc.multi_ratios(got, ref), ' K=%d' % case.steps)
     if not np.isscalar(case.hidden):
         assert_padding_zero(sac)
+    if case.head:
+        assert_clipped_columns_stand_still(case, ci, ref['ls_raw'][:, 0], got)
 
 
 @pytest.mark.parametrize('case', sc.by_group('E'), ids=sc.case_id)
